@@ -3,7 +3,7 @@
 backtracking line search, fp64 (BASELINE.json metric; configs[2] on one GPU, the 1->8 GPU
 series sharding the same n across ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 With --gpus N > 1 and no launcher around it (no RANK in the environment) bench.py is its own
@@ -17,6 +17,12 @@ All vectors are resident in HBM before timing starts. One process per GPU; the s
 path exchanges group partials through the xGMI peer mailboxes (or RCCL all-gathers) inside
 liblbfgs_hip.so; torch.distributed (gloo) is only used for the rendezvous (unique id), barriers,
 votes and the max-over-ranks time.
+
+A plain run sets up, warms up, times the K steps and prints the line. --dump-outputs DIR also
+writes what the timed steps computed (dump_outputs). Everything measured or checked beside the
+headline - the CPU baseline and reference parity, the per-kernel roofline pass, the box probe,
+the vector-free and persistent lines, sharded runs' one-GPU check, exchange timings, RCCL leg and
+configs[4] - runs only with --full; without it those fields of the line are null.
 
 Prints ONE JSON line (rank 0).
 """
@@ -77,7 +83,19 @@ def parse(argv=None):
     p.add_argument("--launch-timeout", type=float, default=float(os.environ.get("BENCH_LAUNCH_TIMEOUT", 3000)),
                    help="--gpus N > 1 without a launcher: seconds before the self-launched ranks are stopped")
     p.add_argument("--no-box-probe", action="store_true", help="skip the in-process HBM stream probe")
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the CPU baseline and reference parity (traced warm-up), the "
+                        "per-kernel roofline pass, the box probe, the vector-free and persistent lines, "
+                        "sharded runs' one-GPU check, exchange timings, RCCL leg and configs[4] "
+                        "(each still has its --no-* switch); off: the headline measurement alone")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what they computed (f, |g| and x, or a fixed seeded "
+                        "sample of a large x) to DIR/<name>.npy")
+    a = p.parse_args(argv)
+    if not a.full:
+        a.no_cpu_baseline = a.no_prof = a.no_box_probe = True
+        a.no_vector_free = a.no_persistent = a.no_config4 = True
+    return a
 
 
 def _free_port():
@@ -361,7 +379,7 @@ def cpu_model():
 
 
 def measure(a, D, n, x0, dev, rank, world, uid, unfused=False, vector_free=False, box_probe=False,
-            defer_rccl=False):
+            defer_rccl=False, dump_dir=None):
     """W warm-up steps, then EXACTLY K timed steps (barrier + device sync on both sides, no
     instrumentation), then a separate event-instrumented pass for per-kernel durations.
 
@@ -380,12 +398,12 @@ def measure(a, D, n, x0, dev, rank, world, uid, unfused=False, vector_free=False
             ctx.close()
         raise err or L.LbfgsError("context creation failed on another rank")
     try:
-        return _measure(a, D, ctx, x0, rank, world, uid, unfused, vector_free, box_probe, defer_rccl)
+        return _measure(a, D, ctx, x0, rank, world, uid, unfused, vector_free, box_probe, defer_rccl, dump_dir)
     finally:
         ctx.close()
 
 
-def _measure(a, D, ctx, x0, rank, world, uid, unfused, vector_free, box_probe, defer_rccl=False):
+def _measure(a, D, ctx, x0, rank, world, uid, unfused, vector_free, box_probe, defer_rccl=False, dump_dir=None):
     failed = []  # this rank's first failure (sticky: later compute is skipped, collectives are not)
 
     def run(fn, *args, **kw):
@@ -411,9 +429,9 @@ def _measure(a, D, ctx, x0, rank, world, uid, unfused, vector_free, box_probe, d
         if not ok and uid is None:
             raise L.LbfgsError("xGMI peer exchange unavailable and no RCCL communicator")  # on every rank
     backend = ctx.backend + ("+fold" if world > 1 and ctx.backend == "xgmi" and ctx.folded else "")
-    # the untimed history fill and warm-up record the trajectory (f, |g|, alpha, x checksums at
-    # the top of every iteration) for reference_parity; the timed steps run untraced
-    trace = not vector_free
+    # --full: the untimed history fill and warm-up record the trajectory (f, |g|, alpha, x checksums
+    # at the top of every iteration) for reference_parity; the timed steps run untraced
+    trace = a.full and not vector_free
     run(ctx.init, a.objective, x0, a.line_search, tolerance=1e-5, unfused=unfused, vector_free=vector_free,
         trace=trace)
     # history fill (untimed, not counted as warm-up): m iterations store m pairs, so every later
@@ -438,6 +456,8 @@ def _measure(a, D, ctx, x0, rank, world, uid, unfused, vector_free, box_probe, d
     T = D.allreduce(t_local, "max")
     bytes_all = D.allreduce(res["bytes"] if res else 0.0, "sum")
     vote("timed steps")
+    if dump_dir and rank == 0:  # before the probe and the profiled steps below move x on
+        run(dump_outputs, ctx, res, dump_dir)
     # this box's rate for the passes' 3 R + 1 W access pattern, on the same buffers, right after
     # the timed steps (bench lines from different boxes are compared against it)
     probe = None
@@ -482,7 +502,7 @@ def _measure(a, D, ctx, x0, rank, world, uid, unfused, vector_free, box_probe, d
     # every rank (collective calls, same sequence everywhere): the two-loop issues ~2h + 3 of
     # them per iteration, each on the critical path
     lat = None
-    if world > 1 and not vector_free and not unfused:
+    if a.full and world > 1 and not vector_free and not unfused:
         lat = {}
         uid_leg = uid is not None
         if backend.startswith("xgmi") and uid is None and a.exchange == "auto" and not defer_rccl:
@@ -507,6 +527,27 @@ def _measure(a, D, ctx, x0, rank, world, uid, unfused, vector_free, box_probe, d
     res["box_probe"] = probe
     done_steps = a.steps if res["status"] == "running" else max(res["iterations"] - a.warmup - fill["iterations"], 1)
     return T, res, prof, bytes_all, done_steps, (backend, lat)
+
+
+DUMP_SAMPLE = 1 << 22  # elements of x written when x is larger (32 MiB of float64)
+
+
+def dump_outputs(ctx, res, dump_dir):
+    """--dump-outputs: what the timed steps' caller receives after the last of them, as float64
+    .npy files: f and gnorm (the step result) and the iterate x (this rank's shard). An x of more
+    than DUMP_SAMPLE elements is written as x_sample: the elements at x_sample_index, a sorted
+    draw from RandomState(20240607) that depends on the length alone, so two builds run with the
+    same arguments write the same elements."""
+    os.makedirs(dump_dir, exist_ok=True)
+    x = ctx.get_x()[:ctx.n_loc]
+    np.save(os.path.join(dump_dir, "f.npy"), np.array([res["f"]], dtype=np.float64))
+    np.save(os.path.join(dump_dir, "gnorm.npy"), np.array([res["gnorm"]], dtype=np.float64))
+    if len(x) <= DUMP_SAMPLE:
+        np.save(os.path.join(dump_dir, "x.npy"), x)
+        return
+    idx = np.unique(np.random.RandomState(20240607).randint(0, len(x), size=DUMP_SAMPLE))
+    np.save(os.path.join(dump_dir, "x_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dump_dir, "x_sample.npy"), x[idx])
 
 
 def exchange_timings(D, ctx, rank, backends, lat, failed):
@@ -904,7 +945,7 @@ def main():
     try:
         T, res, prof, bytes_all, done_steps, (backend, xlat) = measure(a, D, n, x0, dev, rank, world, uid,
                                                       unfused=a.unfused, vector_free=a.vector_free, box_probe=True,
-                                                      defer_rccl=True)
+                                                      defer_rccl=True, dump_dir=a.dump_outputs)
     except L.LbfgsError as e:
         # a mailbox failure across GPUs: measure() raises on every rank together (its votes), so
         # every rank lands here and the line is measured again over RCCL rather than lost, and
@@ -920,8 +961,9 @@ def main():
         uid = D.broadcast_bytes(L.unique_id() if rank == 0 else None)
         need_uid = True
         T, res, prof, bytes_all, done_steps, (backend, xlat) = measure(a, D, n, x0, dev, rank, world, uid,
-                                                      unfused=a.unfused, vector_free=a.vector_free, box_probe=True)
-    check = shard_check(a, D, n, x0, dev, rank, world, res) if world > 1 else None
+                                                      unfused=a.unfused, vector_free=a.vector_free, box_probe=True,
+                                                      dump_dir=a.dump_outputs)
+    check = shard_check(a, D, n, x0, dev, rank, world, res) if world > 1 and a.full else None
     # the opt-in vector-free mode alongside the default (outside the bit-parity contract with
     # the reference's operation order); sharded runs over RCCL need a fresh id
     vf = None

@@ -199,3 +199,44 @@ def test_reference_parity_with_an_x0_only_fixture(bench):
     out = bench.reference_parity(traj, None, fx, src)
     assert out["iterations_compared"] == 1 and out["within_tolerance_iterations"]["f"] == 1
     assert out["canonical"]["bit_exact"] is True
+
+
+def test_plain_run_measures_the_headline_alone(bench):
+    """without --full every measurement or check beside the headline is off (and the warm-up
+    untraced); with it each keeps its own --no-* switch"""
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert plain.steps == 7 and plain.warmup == 3 and not plain.full and plain.dump_outputs is None
+    off = ("no_cpu_baseline", "no_prof", "no_box_probe", "no_vector_free", "no_persistent", "no_config4")
+    assert all(getattr(plain, k) for k in off)
+    full = bench.parse(["--full", "--dump-outputs", "d"])
+    assert full.full and full.dump_outputs == "d" and not any(getattr(full, k) for k in off)
+    assert bench.parse(["--full", "--no-prof"]).no_prof
+
+
+class _FakeCtx:
+    def __init__(self, x, n_loc):
+        self.x, self.n_loc = x, n_loc
+
+    def get_x(self):
+        return self.x.copy()
+
+
+def test_dump_outputs_files(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files of the step result and x; a long x as a sorted sample
+    that depends on its length alone (the same elements from run to run); a shard's own part"""
+    import numpy as np
+
+    x = np.arange(1000, dtype=np.float64) * 0.5
+    res = {"f": 1.25, "gnorm": 3.5}
+    bench.dump_outputs(_FakeCtx(x, 900), res, str(tmp_path / "a"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["f.npy", "gnorm.npy", "x.npy"]
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("f", "gnorm", "x")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["f"].tolist() == [1.25] and got["gnorm"].tolist() == [3.5] and np.array_equal(got["x"], x[:900])
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    for d in ("b", "c"):
+        bench.dump_outputs(_FakeCtx(x, 1000), res, str(tmp_path / d))
+    idx, xs = np.load(tmp_path / "b" / "x_sample_index.npy"), np.load(tmp_path / "b" / "x_sample.npy")
+    assert idx.dtype == xs.dtype == np.float64 and 32 < len(idx) <= 64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(xs, x[idx.astype(np.int64)]) and not os.path.exists(tmp_path / "b" / "x.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "x_sample_index.npy"))

@@ -110,7 +110,7 @@ def _worker(rank, world, port, mode_arg, q):
 
     bench.L.Context = StubContext
     bench.L.unique_id = lambda: bytes(128)
-    a = bench.parse(["--gpus", str(world), "--steps", "5", "--warmup", "2"])
+    a = bench.parse(["--full", "--gpus", str(world), "--steps", "5", "--warmup", "2"])  # the RCCL leg is --full's
     D = bench.Dist(world)
     late = mode_arg.endswith("_late")
     T, res, prof, bytes_all, steps, (backend, lat) = bench.measure(a, D, 10 ** 8, None, 0, rank, world, None,
