@@ -1,0 +1,687 @@
+// lbfgs_kernels_batch.hip — the batched small-n solver (lbfgs_batch_*, include/lbfgs_hip.h): B
+// independent problems that share n, m, objective, line search, constants, tolerance and iteration
+// limit and differ in x0, each solved by ONE workgroup that runs the whole loop of iterate()
+// (lbfgs_driver.c) on the device. A translation unit of its own: twelve large kernels.
+//
+// Every pass walks the problem's canonical segments one after another with the per-segment code of
+// the launch sequence (seg_at, stream, the Op* operators, wave_sum, ((w0 + w1) + (w2 + w3))), so
+// each segment partial is the launch sequence's; the <= 64 partials meet in LDS and one wave forms
+// the group-0 tree and the seven empty groups as coop_pass does. The decisions between the passes
+// are the host's expressions on the same totals, which every thread holds (uniform branches). The
+// result of every problem is therefore bit for bit lbfgs_minimize's for that problem alone.
+// Nothing here waits on another workgroup, a flag or the host: no grid barrier, no time-out.
+#include "lbfgs_hip.h"
+#include "lbfgs_kernels_impl.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+
+#define LBK_BATCH_NMAX 32768       // L = 512 and at most 64 segments: stage 2 is one wave
+#define LBK_BATCH_SEGMAX 64
+#define LBK_BATCH_ITERS 64         // iterations per launch (default)
+#define LBK_BATCH_BTW_CAP 4096     // trial passes of one backtracking_wolfe search (see the header)
+#define LBK_BATCH_NVEC(m) (7 + 2 * ((m) + 1))  // x g xn gn d q r, then the m + 1 pairs (s, y)
+
+namespace {
+
+// one problem's state between launches (device memory; the host reads it after the last launch)
+struct BatchState {
+    int k, h, status, free_pair, sg_valid, flip;  // flip: x/xn and g/gn have changed places
+    int h_min, h_max, tr_len;
+    int ev[4];                                    // not_descent, skipped_updates, invalid_rho, invalid_gamma
+    int ring[LBK_SMALL_HMAX];
+    long long trials_f, trials_fg, commits;
+    double f_cur, gg, sg, vecs;                   // sg: the last commit's s . g_new; vecs: n-vectors streamed
+    double sy[LBK_SMALL_HMAX + 1], yy[LBK_SMALL_HMAX + 1];
+};
+
+struct BatchArgs {
+    int B, m, iters, max_iterations, trace, init, tr_cap;
+    int64_t vstride, pstride;  // doubles per vector / per problem
+    double* base;              // element 0 of vector 0 of problem 0
+    double* xio;               // [B][n]: x0 in, x out
+    BatchState* st;
+    double* tr;                // [B][3][tr_cap]: f, |g|, alpha
+    int* running;              // set when a problem is unfinished at the end of the launch
+    double tol;
+    lbfgs_constants K;
+};
+
+// A problem's scalars are the same in every thread of its workgroup. Held in registers they (the
+// state, the search's variables and caches, the commit's totals: some 250 values) are live across
+// every inlined pass and left the streaming loops no registers; each wave keeps its own copy in LDS
+// instead, every lane storing the same value to the same address, and nothing is read across waves.
+struct BatchWave {
+    BatchState st;
+    lbk_search s;
+    double tot[LBK_KMAX];      // the latest commit's totals
+    double TA[LBK_SMALL_HMAX]; // s_i . q of the first loop
+    double coef, rho_top;      // TWOLOOP: alpha - beta and rho of the last second-loop update
+    int dmode, top, d_ready, capped, passes;
+};
+
+struct BatchLds {
+    double ws[4][LBK_KMAX][LBK_BATCH_SEGMAX];  // wave partials of every segment of the pass
+    double tl[LBK_KMAX];
+    BatchWave wv[4];
+};
+
+#ifndef LBK_BATCH_WAVES
+#define LBK_BATCH_WAVES 0  // A/B: > 0 asks the register allocation for that many waves per SIMD
+#endif
+#if LBK_BATCH_WAVES > 0
+#define LBK_BATCH_ATTR __attribute__((amdgpu_waves_per_eu(LBK_BATCH_WAVES)))
+#else
+#define LBK_BATCH_ATTR
+#endif
+
+// One pass of one problem: the segments in order, each exactly as its workgroup of the launch
+// sequence streams it; then the fixed-order total (coop_pass's nseg <= 64 form). The barrier with
+// its workgroup-scope fences also orders this pass's vector stores before the next pass's loads
+// (other waves' rows, and the stencil halo across a segment seam).
+template <int K, class Op>
+__device__ __forceinline__ void batch_pass(const Op& op, const Geo& geo, BatchLds& L, double* tot) {
+    // the thread index through an empty asm: without it every inlined pass's per-lane addresses
+    // (loop invariants of the iteration loop) are formed at kernel entry and held in registers
+    // throughout - some 250 VGPRs, with spills into the streaming loops
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    const int lane = t & 63, w = t >> 6;
+    const int nseg = (int)geo.nseg;
+    for (int sg = 0; sg < nseg; ++sg) {
+        const Seg s = seg_at(geo, sg, t);
+        double acc[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] = 0.0;
+        stream(op, s, geo, acc);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const double v = wave_sum(acc[k]);
+            if (lane == 0) L.ws[w][k][sg] = v;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+    for (int k = w; k < K; k += 4) {  // wave w: components w, w + 4; lane j: segment j
+        const double p = lane < nseg ? (L.ws[0][k][lane] + L.ws[1][k][lane]) + (L.ws[2][k][lane] + L.ws[3][k][lane]) : 0.0;
+        const double q0 = wave_sum(p) + 0.0;  // group 0: the tree's levels above 64 add 0.0
+        if (lane == 0) {
+            double tt = q0;
+#pragma unroll
+            for (int g = 1; g < LBK_GROUPS; ++g) tt = tt + 0.0;
+            L.tl[k] = tt;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) tot[k] = L.tl[k];
+    __syncthreads();  // ws / tl reuse by the next pass
+}
+
+template <int OBJ, int DMODE, bool CAND>
+__device__ __forceinline__ void batch_commit(const Geo& geo, BatchLds& L, const double* x, const DirArgs& da,
+                                             double alpha, double* xn, double* gn, double* so, double* yo,
+                                             double cand, double* tot) {
+    batch_pass<CAND ? 8 : 7>(OpCommit<OBJ, DMODE, false, CAND>{x, da, alpha, xn, gn, so, yo, geo.n, geo.n_loc, cand},
+                             geo, L, tot);
+}
+
+template <int OBJ, int LS>
+__global__ __launch_bounds__(LB_BLOCK) LBK_BATCH_ATTR void k_batch_solve(BatchArgs a, Geo geo) {
+    __shared__ BatchLds L;
+    constexpr bool FG = LS == 2 || LS == 3;
+    constexpr bool CAND = LS == 0;  // the backtracking search's second step rides the first commit
+    constexpr int NC = LBK_TRIALS_NC;
+    const int t = threadIdx.x, m = a.m;
+    const int64_t n = geo.n;
+    BatchWave& W = L.wv[t >> 6];
+    BatchState& S = W.st;
+    lbk_search& s = W.s;
+    for (int p = blockIdx.x; p < a.B; p += gridDim.x) {
+        BatchState* G = a.st + p;
+        double* vb = a.base + (int64_t)p * a.pstride;
+        auto vec = [&](int i) { return vb + (int64_t)i * a.vstride; };
+        double* const d = vec(4);
+        double* const q = vec(5);
+        double* const r = vec(6);
+        if (a.init) {  // a new solve: x = x0, then f and g.g at x0 (lbfgs.cpp:29-30)
+            S = BatchState();
+            S.status = LBFGS_STATUS_RUNNING;
+            S.h_min = S.h_max = -1;
+            double* x0 = vec(0);
+            for (int64_t i = t; i < n; i += LB_BLOCK) x0[i] = a.xio[(int64_t)p * n + i];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __syncthreads();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            DirArgs da0 = {};
+            double t2[2];
+            batch_pass<2>(OpObjective<OBJ, true, true, false>{x0, da0, 0.0, vec(1), n, n}, geo, L, t2);
+            S.f_cur = t2[0];
+            S.gg = t2[1];
+            S.vecs = 2.0;
+        } else {
+            if (G->status != LBFGS_STATUS_RUNNING) continue;  // uniform: finished in an earlier launch
+            S = *G;
+        }
+        double* trf = a.trace ? a.tr + (int64_t)p * 3 * a.tr_cap : nullptr;
+        auto trace_push = [&](double f, double gn) {
+            if (!trf) return;
+            if (t == 0 && S.tr_len < a.tr_cap) {
+                trf[S.tr_len] = f;
+                trf[a.tr_cap + S.tr_len] = gn;
+                trf[2 * a.tr_cap + S.tr_len] = __builtin_nan("");
+            }
+            S.tr_len++;
+        };
+
+        for (int it = 0; it < a.iters; ++it) {
+            if (S.k >= a.max_iterations) {  // lbfgs.cpp:201-202
+                trace_push(S.f_cur, sqrt(S.gg));
+                S.status = LBFGS_STATUS_MAX_ITER;
+                break;
+            }
+            const int h = S.h;
+            double* const x = vec(S.flip ? 2 : 0);
+            double* const xn = vec(S.flip ? 0 : 2);
+            double* const g = vec(S.flip ? 3 : 1);
+            double* const gn = vec(S.flip ? 1 : 3);
+            double* const so = vec(7 + 2 * S.free_pair);
+            double* const yo = vec(8 + 2 * S.free_pair);
+            const double gnorm = sqrt(S.gg);
+            trace_push(S.f_cur, gnorm);
+            if (gnorm < a.tol) {  // :80-84
+                S.status = LBFGS_STATUS_CONVERGED;
+                break;
+            }
+            if (S.h_min < 0 || h < S.h_min) S.h_min = h;
+            if (h > S.h_max) S.h_max = h;
+
+            // ---- search direction (:87-143) and the fused first trial at a0 with the commit ----
+            const double a0 = a.K.initial_step;
+            const double cand = CAND ? a0 * a.K.backtracking_alpha : 0.0;
+            W.dmode = LBK_D_NEG_G;
+            double gamma = 0.0;
+            if (!(S.k == 0 || h == 0)) {
+                int bad_rho = 0;
+                for (int i = h - 1; i >= 0; --i)
+                    if (!isfinite(1.0 / S.sy[S.ring[i]])) bad_rho = 1;  // :102-108
+                if (bad_rho) {
+                    S.ev[2]++;
+                } else {
+                    const int top = S.ring[h - 1];
+                    gamma = S.sy[top] / S.yy[top];  // :117-118
+                    if (gamma <= 0 || !isfinite(gamma))
+                        S.ev[3]++;
+                    else
+                        W.dmode = LBK_D_TWOLOOP;
+                }
+            }
+            if (W.dmode == LBK_D_TWOLOOP) {
+                const int top = S.ring[h - 1];
+                const double rho_top = 1.0 / S.sy[top];
+                double t1[1];
+                // alpha_{h-1} = rho_{h-1} (s_{h-1} . g): the previous commit's s . g_new, or a dot pass
+                if (S.sg_valid) {
+                    t1[0] = S.sg;
+                } else {
+                    batch_pass<1>(OpDot<false>{vec(7 + 2 * top), g}, geo, L, t1);
+                    S.vecs += 2.0;
+                }
+                W.TA[h - 1] = t1[0];
+                double alpha = rho_top * t1[0];
+                const double* qsrc = g;
+                for (int i = h - 2; i >= 0; --i) {  // q = q - alpha_{i+1} y_{i+1};  s_i . q
+                    batch_pass<1>(OpAxpyDot<false>{q, qsrc, vec(8 + 2 * S.ring[i + 1]), vec(7 + 2 * S.ring[i]), alpha},
+                                  geo, L, t1);
+                    S.vecs += 4.0;
+                    W.TA[i] = t1[0];
+                    alpha = (1.0 / S.sy[S.ring[i]]) * t1[0];
+                    qsrc = q;
+                }
+                batch_pass<1>(OpMid<false>{r, qsrc, vec(8 + 2 * S.ring[0]), alpha, gamma}, geo, L, t1);
+                S.vecs += 3.0;
+                for (int i = 0; i + 1 < h; ++i) {  // r += s_i (alpha_i - beta_i);  y_{i+1} . r
+                    const double rho = 1.0 / S.sy[S.ring[i]];
+                    const double beta = rho * t1[0];
+                    const double alph = rho * W.TA[i];
+                    batch_pass<1>(OpAxpy2Dot<false>{r, r, vec(7 + 2 * S.ring[i]), vec(8 + 2 * S.ring[i + 1]), alph - beta},
+                                  geo, L, t1);
+                    S.vecs += 4.0;
+                }
+                // the last second-loop update rides the commit (k_commit TWOLOOP)
+                const double beta = rho_top * t1[0];
+                const double alph = rho_top * W.TA[h - 1];
+                W.coef = alph - beta;
+                W.rho_top = rho_top;
+                W.top = top;
+            }
+            // how the direction is formed until d is materialised (k_commit's TWOLOOP / NEG_G)
+            auto dir_args = [&]() {
+                DirArgs dd = {};
+                dd.g = g;
+                dd.g_hi = LBK_GROUPS;
+                if (W.dmode == LBK_D_TWOLOOP) {
+                    dd.dsrc = r;
+                    dd.s = vec(7 + 2 * W.top);
+                    dd.coef = W.coef;
+                    dd.rho = W.rho_top;
+                }
+                return dd;
+            };
+            double gd;
+            for (bool fell_back = false;;) {  // the first trial at a0 and the commit, in one pass
+                const DirArgs dd = dir_args();
+                if (W.dmode == LBK_D_TWOLOOP) {
+                    batch_commit<OBJ, LBK_D_TWOLOOP, CAND>(geo, L, x, dd, a0, xn, gn, so, yo, cand, W.tot);
+                    S.vecs += 8.0;
+                } else {
+                    batch_commit<OBJ, LBK_D_NEG_G, CAND>(geo, L, x, dd, a0, xn, gn, so, yo, cand, W.tot);
+                    S.vecs += 6.0;
+                }
+                S.commits++;
+                gd = W.tot[LBK_C_GD];
+                if (!(gd >= 0) || fell_back) break;
+                S.ev[0]++;  // :146-153: not a descent direction, the gradient instead (once, as the host)
+                W.dmode = LBK_D_NEG_G;
+                fell_back = true;
+            }
+
+            // ---- the line search (:156), from the top, with the host's caches ----
+            __builtin_memset(&s, 0, sizeof s);
+            s.f_x = S.f_cur;
+            s.gd = gd;
+            s.c1 = a.K.c1;
+            s.c2 = a.K.c2;
+            s.amin = a.K.wolfe_interp_min;
+            s.init = a.K.initial_step;
+            s.beta = a.K.backtracking_alpha;
+            s.tol = a.K.backtracking_tol;
+            s.have_spec = 1;
+            s.spec_a = a0;
+            s.spec_f = W.tot[LBK_C_F];
+            s.spec_dphi = W.tot[LBK_C_DPHI];
+            if (CAND && cand > 0.0) {
+                s.have_cand = 1;
+                s.cand_a = cand;
+                s.cand_f = W.tot[LBK_C_FC];
+            }
+            s.alpha = a.K.initial_step;
+            s.alpha_hi = INFINITY;
+            s.f_lo = s.f_prev = S.f_cur;
+            s.dphi_lo = gd;
+            W.d_ready = W.capped = W.passes = 0;
+            // d into its buffer before the first pass that reads it (materialize_d: k_last / k_negdot)
+            auto need_d = [&]() {
+                if (W.d_ready) return;
+                double t1[1];
+                if (W.dmode == LBK_D_TWOLOOP) {
+                    batch_pass<1>(OpLast<false>{d, r, vec(7 + 2 * W.top), g, W.coef}, geo, L, t1);
+                    S.vecs += 4.0;
+                } else {
+                    batch_pass<1>(OpNegDot<false>{d, g}, geo, L, t1);
+                    S.vecs += 2.0;
+                }
+                W.d_ready = 1;
+            };
+            auto buf_args = [&]() {
+                DirArgs db = {};
+                db.dsrc = d;
+                db.g = g;
+                db.g_hi = LBK_GROUPS;
+                return db;
+            };
+            auto trial = [&](double alpha, bool need_g, double& f, double& dphi) -> bool {
+                if (search_cached(s, alpha, need_g, f, dphi)) return true;
+                if (LS == 3 && W.passes >= LBK_BATCH_BTW_CAP) {  // the reference's loop has no bound of its own
+                    W.capped = 1;
+                    return false;
+                }
+                need_d();
+                W.passes++;
+                S.vecs += 2.0;
+                if (FG) {
+                    OpTrials<OBJ, LBK_D_BUF, 1, true, false> op{x, buf_args(), {alpha}, n, n};
+                    double tt[2];
+                    batch_pass<2>(op, geo, L, tt);
+                    search_note_fg(s, alpha, tt);
+                    f = tt[0];
+                    dphi = tt[1];
+                } else {
+                    OpTrials<OBJ, LBK_D_BUF, NC, false, false> op{x, buf_args(), {}, n, n};
+                    search_chain<LS>(s, alpha, op.a);
+                    double tt[NC];
+                    batch_pass<NC>(op, geo, L, tt);
+                    search_note_f(s, op.a, tt);
+                    f = tt[0];
+                }
+                return true;
+            };
+            search_loop<LS>(s, trial);
+            S.trials_f += s.passes_f;
+            S.trials_fg += s.passes_fg;
+            if (W.capped || !s.done) {
+                S.status = LBFGS_ERR_STATE;
+                break;
+            }
+            const double alpha = s.step;
+            if (trf && t == 0 && S.tr_len - 1 < a.tr_cap) trf[2 * a.tr_cap + S.tr_len - 1] = alpha;
+
+            // ---- commit (:159-198): again at the search's step when that is not the first trial's ----
+            if (!(alpha == a0)) {
+                need_d();
+                batch_commit<OBJ, LBK_D_BUF, false>(geo, L, x, buf_args(), alpha, xn, gn, so, yo, 0.0, W.tot);
+                S.vecs += 7.0;
+                S.commits++;
+            }
+            S.f_cur = W.tot[LBK_C_F];
+            if (alpha < 1e-10) {  // :164-168
+                S.status = LBFGS_STATUS_LS_FAILED;
+                break;
+            }
+            const double sy = W.tot[LBK_C_SY];
+            if (sy > 0) {  // :182-191
+                const int pair = S.free_pair;
+                if (h >= m) {
+                    const int oldest = S.ring[0];
+                    for (int i = 0; i + 1 < m; ++i) S.ring[i] = S.ring[i + 1];
+                    S.ring[m - 1] = pair;
+                    S.free_pair = oldest;
+                } else {
+                    S.ring[h] = pair;
+                    S.h = h + 1;
+                    S.free_pair = h + 1;  // pool slots 0..h used, h + 1 is free
+                }
+                S.sy[pair] = sy;
+                S.yy[pair] = W.tot[LBK_C_YY];
+                S.sg_valid = 1;
+                S.sg = W.tot[LBK_C_SG];
+            } else {  // :192-195
+                S.ev[1]++;
+                S.sg_valid = 0;
+            }
+            S.flip ^= 1;  // x = x_new, g = g_new (:197-198)
+            S.gg = W.tot[LBK_C_GG];
+            S.k++;
+        }
+
+        if (S.status != LBFGS_STATUS_RUNNING) {  // finished in this launch: x out
+            const double* xc = vec(S.flip ? 2 : 0);
+            for (int64_t i = t; i < n; i += LB_BLOCK) a.xio[(int64_t)p * n + i] = xc[i];
+        }
+        if (t == 0) {
+            *G = S;
+            if (S.status == LBFGS_STATUS_RUNNING) atomicOr(a.running, 1);
+        }
+    }
+}
+
+typedef void (*batch_kernel_t)(BatchArgs, Geo);
+template <int OBJ>
+batch_kernel_t batch_kernel_ls(int ls) {
+    switch (ls) {
+        case 0: return k_batch_solve<OBJ, 0>;
+        case 1: return k_batch_solve<OBJ, 1>;
+        case 2: return k_batch_solve<OBJ, 2>;
+        default: return k_batch_solve<OBJ, 3>;
+    }
+}
+batch_kernel_t batch_kernel(int obj, int ls) {
+    switch (obj) {
+        case LBK_OBJ_ROSENBROCK: return batch_kernel_ls<LBK_OBJ_ROSENBROCK>(ls);
+        case LBK_OBJ_QUAD_TRIDIAG: return batch_kernel_ls<LBK_OBJ_QUAD_TRIDIAG>(ls);
+        default: return batch_kernel_ls<LBK_OBJ_QUAD_SEPARABLE>(ls);
+    }
+}
+
+int64_t batch_vstride(int64_t n) { return LBK_FRONT + ((n + 511) / 512) * 512 + 512; }  // lbk_create's vec_doubles
+
+}  // namespace
+
+struct lbfgs_batch {
+    int64_t n, vstride, pstride;
+    int m, B, device, cus;
+    int max_wg, iters;
+    double* vecs;     // B problems x NVEC vectors, each laid out as lbk_vec_alloc's
+    double* xio;      // [B][n]
+    BatchState* st;
+    int* running;
+    double* tr;       // device trace, [B][3][tr_cap]
+    int tr_cap;
+    hipStream_t stream;
+    std::vector<BatchState> hst;  // the states after the last solve
+    std::vector<double> htr;      // its traces (LBFGS_FLAG_TRACE)
+    int htr_cap;
+    bool solved;
+    Geo geo;
+    char err[256];
+};
+
+#define BHIP(b, expr)                                                                           \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess) {                                                                 \
+            snprintf((b)->err, sizeof (b)->err, "%s: %s", #expr, hipGetErrorString(e_));        \
+            return LBFGS_ERR_HIP;                                                               \
+        }                                                                                       \
+    } while (0)
+
+extern "C" {
+
+int lbfgs_batch_plan(int64_t n, int m, int batch, double* bytes) {
+    if (n < 1 || n > LBK_BATCH_NMAX || m < 1 || m > LBK_SMALL_HMAX || batch < 1) return LBFGS_ERR_BAD_ARG;
+    if (bytes)
+        *bytes = (double)batch * (8.0 * ((double)LBK_BATCH_NVEC(m) * (double)batch_vstride(n) + (double)n) +
+                                  (double)sizeof(BatchState));
+    return 0;
+}
+
+void lbfgs_batch_destroy(lbfgs_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->vecs) (void)hipFree(b->vecs);
+    if (b->xio) (void)hipFree(b->xio);
+    if (b->st) (void)hipFree(b->st);
+    if (b->running) (void)hipFree(b->running);
+    if (b->tr) (void)hipFree(b->tr);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    delete b;
+}
+
+int lbfgs_batch_create(lbfgs_batch** out, int64_t n, int m, int batch, int device) {
+    if (!out) return LBFGS_ERR_BAD_ARG;
+    *out = nullptr;
+    if (lbfgs_batch_plan(n, m, batch, nullptr) != 0) return LBFGS_ERR_BAD_ARG;
+    lbk_geo G;
+    if (lbk_geometry_plan(n, 0, 1, &G) != 0 || G.L != 512 || G.nseg > LBK_BATCH_SEGMAX) return LBFGS_ERR_BAD_ARG;
+    lbfgs_batch* b = new (std::nothrow) lbfgs_batch();
+    if (!b) return LBFGS_ERR_NOMEM;
+    b->n = n;
+    b->m = m;
+    b->B = batch;
+    b->device = device;
+    b->vstride = batch_vstride(n);
+    b->pstride = b->vstride * LBK_BATCH_NVEC(m);
+    b->geo.n = n;
+    b->geo.L = G.L;
+    b->geo.nseg = G.nseg;
+    b->geo.seg_lo = 0;
+    b->geo.elem_lo = 0;
+    b->geo.n_loc = n;
+    b->geo.g_lo = 0;
+    b->geo.g_hi = LBK_GROUPS;
+    b->geo.spg = LBK_SEG_PER_GROUP;
+    b->geo.rev = 0;
+    b->geo.ppart = nullptr;
+    b->geo.edge_slot = nullptr;
+    hipDeviceProp_t prop;
+    const size_t vbytes = sizeof(double) * (size_t)b->pstride * (size_t)batch;
+    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess ||
+        hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipMalloc((void**)&b->vecs, vbytes) != hipSuccess ||
+        hipMalloc((void**)&b->xio, sizeof(double) * (size_t)n * (size_t)batch) != hipSuccess ||
+        hipMalloc((void**)&b->st, sizeof(BatchState) * (size_t)batch) != hipSuccess ||
+        hipMalloc((void**)&b->running, sizeof(int)) != hipSuccess ||
+        // ghost cells and padding are zero and stay zero: no pass stores outside [0, n)
+        hipMemsetAsync(b->vecs, 0, vbytes, b->stream) != hipSuccess ||
+        hipMemsetAsync(b->st, 0, sizeof(BatchState) * (size_t)batch, b->stream) != hipSuccess ||
+        hipStreamSynchronize(b->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        lbfgs_batch_destroy(b);
+        return LBFGS_ERR_HIP;
+    }
+    b->cus = prop.multiProcessorCount;
+    *out = b;
+    return 0;
+}
+
+const char* lbfgs_batch_last_error(const lbfgs_batch* b) { return b ? b->err : "null batch"; }
+
+int lbfgs_batch_set_launch(lbfgs_batch* b, int max_workgroups, int iters_per_launch) {
+    if (!b || max_workgroups < 0 || iters_per_launch < 0) return LBFGS_ERR_BAD_ARG;
+    b->max_wg = max_workgroups;
+    b->iters = iters_per_launch;
+    return 0;
+}
+
+int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const lbfgs_constants* k,
+                         const double* x0_host, double* x_out_host, int max_iterations, double tolerance,
+                         unsigned flags, lbfgs_result* out) {
+    if (!b) return LBFGS_ERR_BAD_ARG;
+    b->err[0] = 0;
+    if (!x0_host || objective < LBFGS_OBJ_ROSENBROCK || objective > LBFGS_OBJ_QUAD_SEPARABLE ||
+        line_search < LBFGS_LS_BACKTRACKING || line_search > LBFGS_LS_BACKTRACKING_WOLFE || max_iterations < 0 ||
+        (flags & ~(LBFGS_FLAG_TRACE | LBFGS_FLAG_QUIET)) != 0) {
+        snprintf(b->err, sizeof b->err, "lbfgs_batch_minimize: device stencil objectives, the four line searches, "
+                 "LBFGS_FLAG_TRACE / LBFGS_FLAG_QUIET only");
+        return LBFGS_ERR_BAD_ARG;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    BHIP(b, hipSetDevice(b->device));
+    b->solved = false;
+    const bool trace = (flags & LBFGS_FLAG_TRACE) != 0;
+    const int tr_cap = max_iterations + 1;  // one entry per iteration's top, one at the exit
+    if (trace && (!b->tr || b->tr_cap < tr_cap)) {
+        if (b->tr) BHIP(b, hipFree(b->tr));
+        b->tr = nullptr;
+        BHIP(b, hipMalloc((void**)&b->tr, sizeof(double) * 3 * (size_t)tr_cap * (size_t)b->B));
+        b->tr_cap = tr_cap;
+    }
+    BatchArgs a;
+    memset(&a, 0, sizeof a);
+    a.B = b->B;
+    a.m = b->m;
+    a.iters = b->iters > 0 ? b->iters : LBK_BATCH_ITERS;
+    a.max_iterations = max_iterations;
+    a.trace = trace;
+    a.init = 1;
+    a.tr_cap = trace ? b->tr_cap : 0;
+    a.vstride = b->vstride;
+    a.pstride = b->pstride;
+    a.base = b->vecs + LBK_FRONT;
+    a.xio = b->xio;
+    a.st = b->st;
+    a.tr = trace ? b->tr : nullptr;
+    a.running = b->running;
+    a.tol = tolerance;
+    if (k)
+        a.K = *k;
+    else
+        lbfgs_constants_default(&a.K);
+    const batch_kernel_t kern = batch_kernel(objective, line_search);
+    int grid = b->max_wg;
+    if (grid <= 0) {  // every workgroup resident: occupancy x CUs
+        int per_cu = 0;
+        BHIP(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, LB_BLOCK, 0));
+        grid = std::max(1, per_cu) * std::max(1, b->cus);
+    }
+    grid = std::min(grid, b->B);
+    // x0 up (one contiguous copy; each workgroup moves its problem's x0 into the vector layout)
+    BHIP(b, hipMemcpyAsync(b->xio, x0_host, sizeof(double) * (size_t)b->n * (size_t)b->B, hipMemcpyHostToDevice,
+                           b->stream));
+    // every launch takes each unfinished problem at least one iteration further, or ends it
+    const long long max_launches = (long long)max_iterations / a.iters + 2;
+    long long launches = 0;
+    for (;;) {
+        int running = 0;
+        BHIP(b, hipMemsetAsync(b->running, 0, sizeof(int), b->stream));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(LB_BLOCK), 0, b->stream, a, b->geo);
+        BHIP(b, hipGetLastError());
+        BHIP(b, hipMemcpyAsync(&running, b->running, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+        BHIP(b, hipStreamSynchronize(b->stream));
+        a.init = 0;
+        ++launches;
+        if (!running) break;
+        if (launches >= max_launches) {
+            snprintf(b->err, sizeof b->err, "lbfgs_batch_minimize: problems unfinished after %lld launches", launches);
+            return LBFGS_ERR_STATE;
+        }
+    }
+    b->hst.resize((size_t)b->B);
+    BHIP(b, hipMemcpyAsync(b->hst.data(), b->st, sizeof(BatchState) * (size_t)b->B, hipMemcpyDeviceToHost, b->stream));
+    if (x_out_host)
+        BHIP(b, hipMemcpyAsync(x_out_host, b->xio, sizeof(double) * (size_t)b->n * (size_t)b->B, hipMemcpyDeviceToHost,
+                               b->stream));
+    b->htr_cap = 0;
+    if (trace) {
+        b->htr.resize(3 * (size_t)b->tr_cap * (size_t)b->B);
+        BHIP(b, hipMemcpyAsync(b->htr.data(), b->tr, sizeof(double) * b->htr.size(), hipMemcpyDeviceToHost, b->stream));
+        b->htr_cap = b->tr_cap;
+    }
+    BHIP(b, hipStreamSynchronize(b->stream));
+    b->solved = true;
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (out)
+        for (int p = 0; p < b->B; ++p) {
+            const BatchState& s = b->hst[(size_t)p];
+            lbfgs_result& r = out[p];
+            memset(&r, 0, sizeof r);
+            r.iterations = s.k;
+            r.status = s.status;
+            r.f = s.f_cur;
+            r.gnorm = sqrt(s.gg);
+            r.trials_f = s.trials_f;
+            r.trials_fg = s.trials_fg;
+            r.commits = s.commits;
+            r.passes = launches;
+            r.bytes = s.vecs * 8.0 * (double)b->n;
+            r.seconds = secs;
+            r.h_min = s.h_min;
+            r.h_max = s.h_min < 0 ? -1 : s.h_max;
+        }
+    return 0;
+}
+
+int lbfgs_batch_trace_len(const lbfgs_batch* b, int problem) {
+    if (!b || problem < 0 || problem >= b->B) return LBFGS_ERR_BAD_ARG;
+    if (!b->solved || !b->htr_cap) return 0;
+    return std::min(b->hst[(size_t)problem].tr_len, b->htr_cap);
+}
+
+int lbfgs_batch_trace_get(const lbfgs_batch* b, int problem, double* f, double* gnorm, double* alpha, int cap) {
+    const int len = lbfgs_batch_trace_len(b, problem);
+    if (len < 0) return len;
+    const int kk = len < cap ? len : cap;
+    const double* base = len ? b->htr.data() + 3 * (size_t)b->htr_cap * (size_t)problem : nullptr;
+    for (int i = 0; i < kk; ++i) {
+        if (f) f[i] = base[i];
+        if (gnorm) gnorm[i] = base[b->htr_cap + i];
+        if (alpha) alpha[i] = base[2 * (size_t)b->htr_cap + i];
+    }
+    return kk < 0 ? 0 : kk;
+}
+
+int lbfgs_batch_events_get(const lbfgs_batch* b, int problem, lbfgs_batch_events* out) {
+    if (!b || !out || problem < 0 || problem >= b->B || !b->solved) return LBFGS_ERR_BAD_ARG;
+    const BatchState& s = b->hst[(size_t)problem];
+    out->not_descent = s.ev[0];
+    out->skipped_updates = s.ev[1];
+    out->invalid_rho = s.ev[2];
+    out->invalid_gamma = s.ev[3];
+    return 0;
+}
+
+}  // extern "C"

@@ -1,9 +1,10 @@
 #pragma once
 // lbfgs_kernels_impl.h — MI355X (gfx950, CDNA4) device layer of the L-BFGS solver: the kernels,
-// the context and the launch helpers, shared by the three translation units that define the
+// the context and the launch helpers, shared by the translation units that define the
 // lbk_* entry points (lbfgs_kernels.hip: lifecycle, two-loop passes, objectives, results;
-// lbfgs_kernels_commit.hip: commit and batched trials; lbfgs_kernels_vf.hip: vector-free mode),
-// compiled in parallel. Everything here has internal linkage.
+// lbfgs_kernels_commit.hip: commit and batched trials; lbfgs_kernels_vf.hip: vector-free mode)
+// and the batched solver (lbfgs_kernels_batch.hip: lbfgs_batch_*), compiled in parallel.
+// Everything here has internal linkage.
 //
 //
 // Every kernel is one streaming pass over fp64 n-vectors that fuses the elementwise work of
@@ -2383,6 +2384,63 @@ __device__ __forceinline__ double search_quad(double a0, double p0, double dp0, 
     return a0 - 0.5 * dp0 * a0 * a0 / (p1 - p0 - dp0 * a0);
 }
 
+// The searches themselves, shared by k_coop_search and the batched solver (k_batch_solve,
+// lbfgs_kernels_batch.hip): the host's caches, the bookkeeping of a trial pass, and the four loops
+// over a caller-supplied trial(alpha, need_g, f, dphi) -> bool (false: no value, the loop stops at
+// the top of its iteration with its variables in s).
+// lbfgs_driver.c trial() / trial_batched() for a device objective: the values the host holds
+__device__ __forceinline__ bool search_cached(const lbk_search& s, double alpha, bool need_g, double& f, double& dphi) {
+    if (s.have_spec && alpha == s.spec_a) {
+        f = s.spec_f;
+        dphi = s.spec_dphi;
+        return true;
+    }
+    if (!need_g && s.have_cand && alpha == s.cand_a) {
+        f = s.cand_f;
+        return true;
+    }
+    // (unrolled over the cache's capacity: a runtime-indexed tc_a[] would put the whole state in scratch)
+#pragma unroll
+    for (int j = 0; j < LBK_TRIALS_NC; ++j)
+        if (j < s.tc_n && alpha == s.tc_a[j] && (!need_g || (j == 0 && s.tc_dphi_ok))) {
+            f = s.tc_f[j];
+            dphi = s.tc_dphi;
+            return true;
+        }
+    return false;
+}
+// the steps of an f-only trial pass from alpha: the search's halving chain
+template <int LS>
+__device__ __forceinline__ void search_chain(const lbk_search& s, double alpha, double (&a)[LBK_TRIALS_NC]) {
+    const double ratio = LS == 0 ? s.beta : 0.5;
+    a[0] = alpha;
+#pragma unroll
+    for (int j = 1; j < LBK_TRIALS_NC; ++j) a[j] = a[j - 1] * ratio;
+}
+// a trial pass's totals become the last-trial-pass cache
+__device__ __forceinline__ void search_note_fg(lbk_search& s, double alpha, const double (&t)[2]) {
+    s.tc_n = 1;
+    s.tc_a[0] = alpha;
+    s.tc_f[0] = t[0];
+    s.tc_dphi = t[1];
+    s.tc_dphi_ok = 1;
+    s.passes_fg++;
+}
+__device__ __forceinline__ void search_note_f(lbk_search& s, const double (&a)[LBK_TRIALS_NC],
+                                              const double (&t)[LBK_TRIALS_NC]) {
+    s.tc_n = LBK_TRIALS_NC;
+#pragma unroll
+    for (int j = 0; j < LBK_TRIALS_NC; ++j) {
+        s.tc_a[j] = a[j];
+        s.tc_f[j] = t[j];
+    }
+    s.tc_dphi = 0.0;
+    s.tc_dphi_ok = 0;
+    s.passes_f++;
+}
+template <int LS, class Trial>
+__device__ __forceinline__ void search_loop(lbk_search& s, Trial&& trial);
+
 template <int OBJ, int LS>
 __global__ __launch_bounds__(LB_BLOCK) void k_coop_search(SmallArgs a, Geo geo, lbk_search s, const double* x,
                                                           const double* d, SearchCommit cm, lbk_search* out) {
@@ -2399,21 +2457,7 @@ __global__ __launch_bounds__(LB_BLOCK) void k_coop_search(SmallArgs a, Geo geo, 
     // false: the launch's pass budget is spent (the state stays at the top of this iteration), or
     // the grid broke apart
     auto trial = [&](double alpha, bool need_g, double& f, double& dphi) -> bool {
-        if (s.have_spec && alpha == s.spec_a) {
-            f = s.spec_f;
-            dphi = s.spec_dphi;
-            return true;
-        }
-        if (!need_g && s.have_cand && alpha == s.cand_a) {
-            f = s.cand_f;
-            return true;
-        }
-        for (int j = 0; j < s.tc_n; ++j)
-            if (alpha == s.tc_a[j] && (!need_g || (j == 0 && s.tc_dphi_ok))) {
-                f = s.tc_f[j];
-                dphi = s.tc_dphi;
-                return true;
-            }
+        if (search_cached(s, alpha, need_g, f, dphi)) return true;
         if (pass >= LBK_SEARCH_PASSES || broken) return false;
         if (FG) {
             OpTrials<OBJ, LBK_D_BUF, 1, true, false> op{x, da, {alpha}, geo.n, geo.n_loc};
@@ -2422,38 +2466,52 @@ __global__ __launch_bounds__(LB_BLOCK) void k_coop_search(SmallArgs a, Geo geo, 
                 broken = true;
                 return false;
             }
-            s.tc_n = 1;
-            s.tc_a[0] = alpha;
-            s.tc_f[0] = t[0];
-            s.tc_dphi = t[1];
-            s.tc_dphi_ok = 1;
-            s.passes_fg++;
+            search_note_fg(s, alpha, t);
             f = t[0];
             dphi = t[1];
         } else {
-            const double ratio = LS == 0 ? s.beta : 0.5;  // the search's halving chain
             OpTrials<OBJ, LBK_D_BUF, NC, false, false> op{x, da, {}, geo.n, geo.n_loc};
-            op.a[0] = alpha;
-#pragma unroll
-            for (int j = 1; j < NC; ++j) op.a[j] = op.a[j - 1] * ratio;
+            search_chain<LS>(s, alpha, op.a);
             double t[NC];
             if (!coop_pass<NC>(op, geo, a, pass++, nullptr, nullptr, nullptr, t, lds, tl)) {
                 broken = true;
                 return false;
             }
-            s.tc_n = NC;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                s.tc_a[j] = op.a[j];
-                s.tc_f[j] = t[j];
-            }
-            s.tc_dphi = 0.0;
-            s.tc_dphi_ok = 0;
-            s.passes_f++;
+            search_note_f(s, op.a, t);
             f = t[0];
         }
         return true;
     };
+    search_loop<LS>(s, trial);
+    // the commit at the decided step (lbfgs_driver.c commit(), D_BUF, cand 0), unless the commit
+    // already taken was at that step
+    // (a workgroup whose barriers all completed can still reach this pass while another one timed
+    // out at the last trial barrier; it then writes its own segments of xn, gn, s and y, which is
+    // why the host's redo commits again even at the first trial's step, recommit_a0)
+    if (!broken && s.done && cm.slot && !(s.have_spec && s.step == s.spec_a)) {
+        DirArgs dc = {d, nullptr, cm.g, 0.0, nullptr, nullptr, 0.0, nullptr, geo.g_lo, geo.g_hi};
+        double t7[7];
+        coop_pass<7>(OpCommit<OBJ, LBK_D_BUF, false>{x, dc, s.step, cm.xn, cm.gn, cm.so, cm.yo, geo.n, geo.n_loc,
+                                                      0.0},
+                     geo, a, pass++, cm.slot, cm.hslot, nullptr, t7, lds, tl);
+        s.committed = 1;
+    }
+    // block 0: the search state, then the completion word the host polls (lbk_search_dev): block 0
+    // leaves only after every barrier of the launch completed or failed, and a failure has set the
+    // error flag before this word
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) *out = s;
+        if (a.done) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+            __syncthreads();
+            if (threadIdx.x == 0) __hip_atomic_store(a.done, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// the four loops (s.alpha and the search's own variables: at the top of an iteration, in and out)
+template <int LS, class Trial>
+__device__ __forceinline__ void search_loop(lbk_search& s, Trial&& trial) {
     auto finish = [&](double step) {
         s.done = 1;
         s.step = step;
@@ -2576,30 +2634,6 @@ __global__ __launch_bounds__(LB_BLOCK) void k_coop_search(SmallArgs a, Geo geo, 
         }
     }
     s.alpha = alpha;
-    // the commit at the decided step (lbfgs_driver.c commit(), D_BUF, cand 0), unless the commit
-    // already taken was at that step
-    // (a workgroup whose barriers all completed can still reach this pass while another one timed
-    // out at the last trial barrier; it then writes its own segments of xn, gn, s and y, which is
-    // why the host's redo commits again even at the first trial's step, recommit_a0)
-    if (!broken && s.done && cm.slot && !(s.have_spec && s.step == s.spec_a)) {
-        DirArgs dc = {d, nullptr, cm.g, 0.0, nullptr, nullptr, 0.0, nullptr, geo.g_lo, geo.g_hi};
-        double t7[7];
-        coop_pass<7>(OpCommit<OBJ, LBK_D_BUF, false>{x, dc, s.step, cm.xn, cm.gn, cm.so, cm.yo, geo.n, geo.n_loc,
-                                                      0.0},
-                     geo, a, pass++, cm.slot, cm.hslot, nullptr, t7, lds, tl);
-        s.committed = 1;
-    }
-    // block 0: the search state, then the completion word the host polls (lbk_search_dev): block 0
-    // leaves only after every barrier of the launch completed or failed, and a failure has set the
-    // error flag before this word
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) *out = s;
-        if (a.done) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-            __syncthreads();
-            if (threadIdx.x == 0) __hip_atomic_store(a.done, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------

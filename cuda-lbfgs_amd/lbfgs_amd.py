@@ -51,6 +51,14 @@ class Result(C.Structure):
         return d
 
 
+class BatchEvents(C.Structure):
+    _fields_ = [("not_descent", C.c_int), ("skipped_updates", C.c_int), ("invalid_rho", C.c_int),
+                ("invalid_gamma", C.c_int)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 HOST_F = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_int64, C.c_void_p)
 HOST_G = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_void_p)
 
@@ -136,6 +144,18 @@ def lib():
     L.lbfgs_prof_reset.restype = None
     L.lbfgs_prof_get.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                  C.POINTER(C.c_double)]
+    L.lbfgs_batch_plan.argtypes = [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.lbfgs_batch_create.argtypes = [C.POINTER(vp), C.c_int64, C.c_int, C.c_int, C.c_int]
+    L.lbfgs_batch_destroy.argtypes = [vp]
+    L.lbfgs_batch_destroy.restype = None
+    L.lbfgs_batch_last_error.argtypes = [vp]
+    L.lbfgs_batch_last_error.restype = C.c_char_p
+    L.lbfgs_batch_set_launch.argtypes = [vp, C.c_int, C.c_int]
+    L.lbfgs_batch_minimize.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Constants), dp, dp, C.c_int, C.c_double,
+                                       C.c_uint, C.POINTER(Result)]
+    L.lbfgs_batch_trace_len.argtypes = [vp, C.c_int]
+    L.lbfgs_batch_trace_get.argtypes = [vp, C.c_int, dp, dp, dp, C.c_int]
+    L.lbfgs_batch_events_get.argtypes = [vp, C.c_int, C.POINTER(BatchEvents)]
     _lib = L
     return L
 
@@ -152,6 +172,9 @@ EXPORTED_SYMBOLS = [
     "lbfgs_prof_reset", "lbfgs_prof_get", "lbfgs_peer_handle", "lbfgs_peer_connect", "lbfgs_peer_enable", "lbfgs_rccl_attach",
     "lbfgs_exchange_backend", "lbfgs_exchange_fold", "lbfgs_exchange_latency", "lbfgs_device_count", "lbfgs_set_dense_quadratic", "lbfgs_build_info",
     "lbfgs_spec_stats", "lbfgs_cu_partition", "lbfgs_stream_probe", "lbfgs_stream_probe_variant", "lbfgs_stream_probe_vectors", "lbfgs_vector_address", "lbfgs_coop_info", "lbfgs_wait_stats", "lbfgs_vector_fallbacks", "lbfgs_vector_pool", "lbfgs_search_stats",
+    "lbfgs_batch_plan", "lbfgs_batch_create", "lbfgs_batch_destroy", "lbfgs_batch_last_error",
+    "lbfgs_batch_set_launch", "lbfgs_batch_minimize", "lbfgs_batch_trace_len", "lbfgs_batch_trace_get",
+    "lbfgs_batch_events_get",
 ]
 PEER_HANDLE_BYTES = 64
 BACKENDS = {0: "single", 1: "rccl", 2: "xgmi", 3: "host-group"}
@@ -243,6 +266,121 @@ class HostGroup:
             self.close()
         except Exception:
             pass
+
+
+def plan(n, m, batch):
+    """Device bytes a Batch(n, m, batch) would take (no device needed); raises LbfgsError when
+    (n, m, batch) is outside the batched solver's limits (lbfgs_batch_plan)."""
+    b = C.c_double()
+    rc = lib().lbfgs_batch_plan(int(n), int(m), int(batch), C.byref(b))
+    if rc != 0:
+        e = LbfgsError(f"lbfgs_batch_plan({n}, {m}, {batch}) failed ({rc}): 1 <= n <= 32768, 1 <= m <= 16, batch >= 1")
+        e.rc = rc
+        raise e
+    return b.value
+
+
+class Batch:
+    """`batch` independent small problems (same n, m, objective, line search, constants, tolerance
+    and iteration limit; their own x0) solved at once, one workgroup each, the whole solver loop on
+    the device; every problem's result is bit for bit Context.minimize's for it alone.
+
+        with L.Batch(n=10_000, m=5, batch=256) as b:
+            res = b.minimize("rosenbrock", X0, "backtracking", max_iterations=100)   # X0: 256 x n
+    """
+
+    def __init__(self, n, m, batch, device=0):
+        self.n, self.m, self.batch = int(n), int(m), int(batch)
+        h = C.c_void_p()
+        rc = lib().lbfgs_batch_create(C.byref(h), self.n, self.m, self.batch, int(device))
+        if rc != 0:
+            e = LbfgsError(f"lbfgs_batch_create failed ({rc})")
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().lbfgs_batch_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _err(self, what, rc):
+        msg = lib().lbfgs_batch_last_error(self.h)
+        e = LbfgsError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+        e.rc = rc
+        raise e
+
+    def set_launch(self, max_workgroups=0, iters_per_launch=0):
+        """Tuning only (results do not depend on it): workgroups per launch and iterations a launch
+        takes every unfinished problem further; 0 = the default for either."""
+        rc = lib().lbfgs_batch_set_launch(self.h, int(max_workgroups), int(iters_per_launch))
+        if rc != 0:
+            self._err("lbfgs_batch_set_launch", rc)
+
+    def minimize(self, objective, X0, line_search="backtracking", max_iterations=1000, tolerance=1e-5,
+                 consts=None, trace=False, flags=0, out=None):
+        """X0: batch x n. Returns per-problem arrays x (batch x n), f, gnorm, iterations, status
+        (names; status_code: the numbers), commits, trials_f, trials_fg, h_min, h_max, bytes, and the
+        call's launches and seconds; with trace also the lists tr_f / tr_gnorm / tr_alpha and events.
+        flags: further LBFGS_FLAG_* bits, passed through (the library refuses what a batch cannot do)."""
+        X0 = np.ascontiguousarray(X0, dtype=np.float64)
+        assert X0.shape == (self.batch, self.n)
+        if out is not None:
+            assert out.dtype == np.float64 and out.shape == X0.shape and out.flags["C_CONTIGUOUS"]
+        X = out if out is not None else np.zeros_like(X0)
+        res = (Result * self.batch)()
+        k = consts if consts is not None else constants()
+        fl = FLAG_QUIET | (FLAG_TRACE if trace else 0) | int(flags)
+        obj = OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        rc = lib().lbfgs_batch_minimize(self.h, obj, LINE_SEARCHES[line_search], C.byref(k), X0, X,
+                                        int(max_iterations), float(tolerance), fl, res)
+        if rc < 0:
+            self._err("lbfgs_batch_minimize", rc)
+        col = lambda name, dt: np.array([getattr(r, name) for r in res], dtype=dt)  # noqa: E731
+        code = col("status", np.int64)
+        d = dict(x=X, f=col("f", np.float64), gnorm=col("gnorm", np.float64), iterations=col("iterations", np.int64),
+                 status=[STATUS.get(int(s), int(s)) for s in code], status_code=code,
+                 commits=col("commits", np.int64), trials_f=col("trials_f", np.int64),
+                 trials_fg=col("trials_fg", np.int64), h_min=col("h_min", np.int64), h_max=col("h_max", np.int64),
+                 bytes=col("bytes", np.float64), launches=int(res[0].passes), seconds=float(res[0].seconds))
+        if trace:
+            d["tr_f"], d["tr_gnorm"], d["tr_alpha"], d["events"] = [], [], [], []
+            for p in range(self.batch):
+                f, g, a = self.trace(p)
+                d["tr_f"].append(f)
+                d["tr_gnorm"].append(g)
+                d["tr_alpha"].append(a)
+                d["events"].append(self.events(p))
+        return d
+
+    def trace(self, problem):
+        """(f, |g|, alpha) per iteration of one problem of the last traced solve"""
+        n = lib().lbfgs_batch_trace_len(self.h, int(problem))
+        if n < 0:
+            self._err("lbfgs_batch_trace_len", n)
+        f, g, a = np.empty(max(n, 1)), np.empty(max(n, 1)), np.empty(max(n, 1))
+        lib().lbfgs_batch_trace_get(self.h, int(problem), f, g, a, n)
+        return f[:n], g[:n], a[:n]
+
+    def events(self, problem):
+        """dict(not_descent, skipped_updates, invalid_rho, invalid_gamma) of one problem of the last solve"""
+        ev = BatchEvents()
+        rc = lib().lbfgs_batch_events_get(self.h, int(problem), C.byref(ev))
+        if rc != 0:
+            self._err("lbfgs_batch_events_get", rc)
+        return ev.as_dict()
 
 
 class Context:

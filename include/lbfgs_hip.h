@@ -331,6 +331,47 @@ int lbfgs_trace_get(const lbfgs_ctx* ctx, double* f, double* gnorm, double* alph
  * extra passes) */
 int lbfgs_trace_enable(lbfgs_ctx* ctx, int on);
 
+/* ---- many small problems at once ------------------------------------------------------- */
+/* A batch solves `batch` independent problems that share n, m, objective, line search, constants,
+ * tolerance and iteration limit and differ only in x0, one workgroup per problem, the whole loop of
+ * lbfgs_minimize on the device: no host round trip per iteration, hundreds of
+ * problems side by side. Each problem's x, f, |g|, iterations, status and trace are bit for bit what
+ * lbfgs_minimize gives for that problem alone. Limits: 1 <= n <= 32768, 1 <= m <= 16, the device
+ * stencil objectives (LBFGS_OBJ_ROSENBROCK, _QUAD_TRIDIAG, _QUAD_SEPARABLE), the four line searches,
+ * one GPU, flags LBFGS_FLAG_TRACE and LBFGS_FLAG_QUIET (a batch prints nothing; quiet is implied);
+ * anything else is LBFGS_ERR_BAD_ARG before anything is launched.
+ * The one deliberate difference from the single-problem path: the reference's backtracking_wolfe
+ * loop (line_search.cpp:33-55) has no bound of its own; here a search that reaches 4096 trial
+ * passes ends its problem with status LBFGS_ERR_STATE in that problem's result, the others go on. */
+typedef struct lbfgs_batch lbfgs_batch;
+/* no device needed: 0 when (n, m, batch) is within the batched solver's limits, else
+ * LBFGS_ERR_BAD_ARG; *bytes (nullable) = device memory the batch would take (traces apart) */
+int lbfgs_batch_plan(int64_t n, int m, int batch, double* bytes);
+int lbfgs_batch_create(lbfgs_batch** out, int64_t n, int m, int batch, int device);
+void lbfgs_batch_destroy(lbfgs_batch* b);
+const char* lbfgs_batch_last_error(const lbfgs_batch* b);
+/* tuning, results unaffected: 0 = default for either (workgroups: occupancy x CUs, at most one per
+ * problem; iterations a launch takes every unfinished problem further: 64) */
+int lbfgs_batch_set_launch(lbfgs_batch* b, int max_workgroups, int iters_per_launch);
+/* x0_host / x_out_host: batch x n doubles, problem p at offset p * n; out: batch entries (either
+ * output may be NULL). Returns 0, or an error for bad arguments or a HIP failure only: a problem
+ * that does not converge says so in its own status. Per entry of out: iterations, status, f, gnorm,
+ * h_min / h_max, and trials_f / trials_fg / commits as the kernel counted that problem's passes;
+ * bytes = that problem's algorithmic bytes; passes = kernel launches of the whole call and
+ * seconds = wall time of the whole call, the same in every entry; f_calls = grad_calls = 0.
+ * A batch object serves any number of calls. */
+int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const lbfgs_constants* k,
+                         const double* x0_host, double* x_out_host, int max_iterations,
+                         double tolerance, unsigned flags, lbfgs_result* out);
+/* LBFGS_FLAG_TRACE: the entries lbfgs_trace_get gives for problem p solved alone (f, |g|, alpha) */
+int lbfgs_batch_trace_len(const lbfgs_batch* b, int problem);
+int lbfgs_batch_trace_get(const lbfgs_batch* b, int problem, double* f, double* gnorm,
+                          double* alpha, int cap);
+/* what the single-problem path would have printed, as counts: "Not a descent direction",
+ * "Skipping update", "Invalid rho", "Invalid gamma" (a failed line search is the status) */
+typedef struct { int not_descent, skipped_updates, invalid_rho, invalid_gamma; } lbfgs_batch_events;
+int lbfgs_batch_events_get(const lbfgs_batch* b, int problem, lbfgs_batch_events* out);
+
 /* ---- line search alone (line_search.h:10-26 on the GPU) -------------------------------- */
 /* Step size along d from x (gradient g at x) by one of the four line searches, every trial on
  * the device (or through cb for LBFGS_OBJ_HOST). Single rank; ends any solve in progress. */
