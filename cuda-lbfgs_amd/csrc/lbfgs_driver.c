@@ -94,6 +94,9 @@ struct lbfgs_ctx {
     double hf_alpha, hf_val;
     int refcalls; /* LBFGS_FLAG_REFERENCE_CALLS */
     int dense_set; /* lbfgs_set_dense_quadratic called */
+    /* device-callback objective (LBFGS_OBJ_DEVICE): the caller's eval on solver-owned device
+     * memory; dcb.eval == NULL: none set */
+    lbfgs_device_fn dcb;
     int64_t cb_f, cb_g;
     /* per-iteration working state */
     int dmode, d_ready;
@@ -463,6 +466,16 @@ int lbfgs_set_dense_quadratic(lbfgs_ctx* c, const double* A, const double* b) {
     return 0;
 }
 
+int lbfgs_set_device_objective(lbfgs_ctx* c, const lbfgs_device_fn* fn) {
+    if (!c || (fn && (!fn->eval || c->geo->world != 1))) return LBFGS_ERR_BAD_ARG;
+    if (c->inited && c->obj == LBFGS_OBJ_DEVICE) c->inited = 0; /* a solve in progress loses its objective */
+    if (fn)
+        c->dcb = *fn;
+    else
+        memset(&c->dcb, 0, sizeof c->dcb);
+    return 0;
+}
+
 int lbfgs_exchange_backend(const lbfgs_ctx* c) { return c ? lbk_exchange_backend(c->dev) : LBFGS_ERR_BAD_ARG; }
 int lbfgs_exchange_fold(const lbfgs_ctx* c) { return c ? lbk_exchange_fold(c->dev) : LBFGS_ERR_BAD_ARG; }
 
@@ -580,10 +593,30 @@ int lbfgs_stream_probe_vectors(lbfgs_ctx* c, int qk, int yk, int sk, int launche
 #define XF_X 1
 #define XF_G0 2 /* + buffer */
 
-/* objectives evaluated outside the fused stencil passes: host callbacks, and the dense quadratic
- * (a matrix-vector product needs the whole trial point first). Both run the same driver path:
- * z = x + alpha d formed on the device, f / grad at z, the commit with the gradient supplied. */
-static int ext_obj(const lbfgs_ctx* c) { return c->obj == LBFGS_OBJ_HOST || c->obj == LBFGS_OBJ_DENSE_QUAD; }
+/* objectives evaluated outside the fused stencil passes: host callbacks, the dense quadratic
+ * (a matrix-vector product needs the whole trial point first) and device callbacks. All run the
+ * same driver path: z = x + alpha d formed on the device, f / grad at z, the commit with the
+ * gradient supplied. */
+static int ext_obj(const lbfgs_ctx* c) {
+    return c->obj == LBFGS_OBJ_HOST || c->obj == LBFGS_OBJ_DENSE_QUAD || c->obj == LBFGS_OBJ_DEVICE;
+}
+/* ... whose trial point and gradient never leave the device */
+static int resident_obj(const lbfgs_ctx* c) { return c->obj == LBFGS_OBJ_DENSE_QUAD || c->obj == LBFGS_OBJ_DEVICE; }
+
+/* One call of the device callback (LBFGS_OBJ_DEVICE) at the solver vector z: f into *f and / or the
+ * gradient into the solver vector g. Every launch that produced z has completed when eval is
+ * entered; eval returns with its own work on g complete (include/lbfgs_hip.h). */
+static int device_eval(lbfgs_ctx* c, const double* z, double* f, double* g) {
+    DEVNC(lbk_sync(c->dev));
+    const int rc = c->dcb.eval(z, c->n, f, g, c->dcb.user);
+    if (f) c->cb_f++;
+    if (g) c->cb_g++;
+    if (rc != 0) {
+        snprintf(c->err, sizeof c->err, "device objective callback returned %d", rc);
+        return LBFGS_ERR_CALLBACK;
+    }
+    return 0;
+}
 
 static int host_bufs(lbfgs_ctx* c) {
     const size_t b = sizeof(double) * (size_t)c->n;
@@ -606,7 +639,7 @@ static int host_point_issue(lbfgs_ctx* c, double alpha) {
     if (c->hz_valid && c->hz_alpha == alpha) return 0;
     if (c->hz_pending) DEVNC(lbk_xfer_wait(c->dev, XF_Z)); /* hx is still being written */
     DEV(lbk_point(c->dev, c->xn, c->x, c->d, alpha));
-    if (c->obj == LBFGS_OBJ_DENSE_QUAD) { /* z stays on the device (xn) */
+    if (resident_obj(c)) { /* z stays on the device (xn) */
         c->hz_valid = 1;
         c->hz_pending = 0;
         c->hz_alpha = alpha;
@@ -643,6 +676,15 @@ static int host_f_at(lbfgs_ctx* c, double alpha, int fresh, double* f) {
         DEVNC(lbk_fetch(c->dev, SLOT_TRIAL(c->m), 1, f));
         c->gt_valid = 1;
         c->gt_alpha = alpha;
+    } else if (c->obj == LBFGS_OBJ_DEVICE) {
+        /* LBFGS_DEVICE_EAGER_GRAD: the gradient with every f, into gt as the dense objective's */
+        const int eager = (c->dcb.flags & LBFGS_DEVICE_EAGER_GRAD) != 0;
+        rc = device_eval(c, c->xn, f, eager ? c->gt : NULL);
+        if (rc) return rc;
+        if (eager) {
+            c->gt_valid = 1;
+            c->gt_alpha = alpha;
+        }
     } else {
         *f = c->cb.f(c->hx, c->n, c->cb.user);
         c->cb_f++;
@@ -668,6 +710,24 @@ static int host_g_at(lbfgs_ctx* c, double alpha, int fresh, double* dst) {
         c->hf_valid = 1;
         c->hf_alpha = alpha;
         c->hf_val = f;
+        if (dst == c->gt) {
+            c->gt_valid = 1;
+            c->gt_alpha = alpha;
+        } else if (c->gt_valid && c->gt_alpha == alpha) {
+            c->gt_valid = 0;
+        }
+        return 0;
+    }
+    if (c->obj == LBFGS_OBJ_DEVICE) { /* f with it where this point's is not cached yet */
+        const int need_f = !(c->hf_valid && c->hf_alpha == alpha);
+        double f = 0.0;
+        rc = device_eval(c, c->xn, need_f ? &f : NULL, dst);
+        if (rc) return rc;
+        if (need_f) {
+            c->hf_valid = 1;
+            c->hf_alpha = alpha;
+            c->hf_val = f;
+        }
         if (dst == c->gt) {
             c->gt_valid = 1;
             c->gt_alpha = alpha;
@@ -2402,13 +2462,36 @@ static int iterate_cuda(lbfgs_ctx* c) {
 }
 #undef CU
 
-int lbfgs_solver_init(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int line_search,
-                      const lbfgs_constants* k, const double* x0_host, double tolerance,
-                      unsigned flags) {
-    if (!c || !x0_host) return LBFGS_ERR_BAD_ARG;
-    if (objective < 0 || objective > LBFGS_OBJ_DENSE_QUAD) return LBFGS_ERR_BAD_ARG;
+/* Caller-owned device buffers (the _device entry points): n doubles, unpadded, 8-byte aligned. The
+ * streaming passes assume lbk_vec_alloc's layout (ghost cells, zeroed padding, 16-byte rows) and are
+ * never launched on one; a buffer is copied to or from a solver vector by one pass of the
+ * elementwise kernel on the solver stream, which reads and writes exactly [0, n) (op 0 with
+ * alpha = 1.0 keeps every double value). */
+static int import_device(lbfgs_ctx* c, double* dst, const double* src_dev) {
+    DEV(lbk_elementwise(c->dev, 0, dst, src_dev, NULL, 1.0));
+    return 0;
+}
+
+static int export_device(lbfgs_ctx* c, double* dst_dev, const double* src) {
+    DEV(lbk_elementwise(c->dev, 0, dst_dev, src, NULL, 1.0));
+    DEVNC(lbk_sync(c->dev)); /* complete on return */
+    return 0;
+}
+
+/* x0_dev != 0: x0 is a caller-owned device buffer (lbfgs_solver_init_device) */
+static int solver_init_at(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int line_search,
+                          const lbfgs_constants* k, const double* x0, int x0_dev, double tolerance,
+                          unsigned flags) {
+    if (!c || !x0) return LBFGS_ERR_BAD_ARG;
+    if (objective < 0 || objective > LBFGS_OBJ_DEVICE) return LBFGS_ERR_BAD_ARG;
     if (line_search < 0 || line_search > LBFGS_LS_BACKTRACKING_WOLFE) return LBFGS_ERR_BAD_ARG;
+    if (x0_dev && c->geo->world != 1) return LBFGS_ERR_BAD_ARG;
     if (objective == LBFGS_OBJ_DENSE_QUAD && !c->dense_set) return LBFGS_ERR_STATE;
+    if (objective == LBFGS_OBJ_DEVICE) { /* one rank, the default driver path only */
+        if (!c->dcb.eval || c->geo->world != 1) return LBFGS_ERR_BAD_ARG;
+        if (flags & (LBFGS_FLAG_UNFUSED | LBFGS_FLAG_VECTOR_FREE | LBFGS_FLAG_REFERENCE_CALLS | LBFGS_FLAG_CUDA_COMPAT))
+            return LBFGS_ERR_BAD_ARG;
+    }
     c->refcalls = (flags & LBFGS_FLAG_REFERENCE_CALLS) != 0;
     if (objective == LBFGS_OBJ_HOST) {
         if (!cb || !cb->f || !cb->grad || c->geo->world != 1) return LBFGS_ERR_BAD_ARG;
@@ -2480,8 +2563,23 @@ int lbfgs_solver_init(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int 
     c->tr_len = 0;
     c->trials_f = c->trials_fg = c->commits = c->passes = 0;
 
-    DEVNC(lbk_upload(c->dev, c->x, x0_host)); /* x = x0 */
-    if (objective == LBFGS_OBJ_HOST) {         /* :29-30 */
+    const double* x0_host = x0;
+    if (x0_dev) { /* x = x0 */
+        const int rc = import_device(c, c->x, x0);
+        if (rc) return rc;
+        if (objective == LBFGS_OBJ_HOST) { /* the callbacks read x0 from the pinned point buffer */
+            DEVNC(lbk_download_local(c->dev, c->hx, c->x));
+            x0_host = c->hx;
+        }
+    } else {
+        DEVNC(lbk_upload(c->dev, c->x, x0));
+    }
+    if (objective == LBFGS_OBJ_DEVICE) {
+        const int rc = device_eval(c, c->x, &c->f_cur, c->g);
+        if (rc) return rc;
+        DEV(lbk_dot(c->dev, c->g, c->g, SLOT_INIT));
+        DEVNC(lbk_fetch(c->dev, SLOT_INIT, 1, &c->gg));
+    } else if (objective == LBFGS_OBJ_HOST) {  /* :29-30 */
         c->f_cur = c->cb.f(x0_host, c->n, c->cb.user);
         const int b = c->hg_cur;
         c->hg_cur ^= 1;
@@ -2510,6 +2608,18 @@ int lbfgs_solver_init(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int 
     }
     c->inited = 1;
     return 0;
+}
+
+int lbfgs_solver_init(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int line_search,
+                      const lbfgs_constants* k, const double* x0_host, double tolerance,
+                      unsigned flags) {
+    return solver_init_at(c, objective, cb, line_search, k, x0_host, 0, tolerance, flags);
+}
+
+int lbfgs_solver_init_device(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int line_search,
+                             const lbfgs_constants* k, const double* x0_dev, double tolerance,
+                             unsigned flags) {
+    return solver_init_at(c, objective, cb, line_search, k, x0_dev, 1, tolerance, flags);
 }
 
 static void fill_result(lbfgs_ctx* c, lbfgs_result* out, double t0, double b0) {
@@ -2563,13 +2673,19 @@ int lbfgs_get_x(lbfgs_ctx* c, double* x_out_host) {
     return 0;
 }
 
-int lbfgs_minimize(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int line_search,
-                   const lbfgs_constants* k, const double* x0_host, double* x_out_host,
-                   int max_iterations, double tolerance, unsigned flags, lbfgs_result* out) {
+int lbfgs_get_x_device(lbfgs_ctx* c, double* x_out_dev) {
+    if (!c || !x_out_dev || c->geo->world != 1) return LBFGS_ERR_BAD_ARG;
+    return export_device(c, x_out_dev, c->x);
+}
+
+/* dev != 0: x0 and x_out are caller-owned device buffers (lbfgs_minimize_device) */
+static int minimize_at(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int line_search,
+                       const lbfgs_constants* k, const double* x0, double* x_out, int dev,
+                       int max_iterations, double tolerance, unsigned flags, lbfgs_result* out) {
     const double t0 = now_s();
     if (!c) return LBFGS_ERR_BAD_ARG;
     const double b0 = lbk_bytes_moved(c->dev);
-    int rc = lbfgs_solver_init(c, objective, cb, line_search, k, x0_host, tolerance, flags);
+    int rc = solver_init_at(c, objective, cb, line_search, k, x0, dev, tolerance, flags);
     if (rc) return rc;
     rc = lbfgs_solver_step(c, max_iterations, NULL); /* sets h_min / h_max for the whole solve */
     if (rc < 0) return rc;
@@ -2582,12 +2698,26 @@ int lbfgs_minimize(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int lin
         c->status = LBFGS_STATUS_MAX_ITER;
         c->finished = 1;
     }
-    if (x_out_host) {
-        rc = lbfgs_get_x(c, x_out_host);
+    if (x_out) {
+        rc = dev ? lbfgs_get_x_device(c, x_out) : lbfgs_get_x(c, x_out);
         if (rc) return rc;
     }
     fill_result(c, out, t0, b0);
     return c->status;
+}
+
+int lbfgs_minimize(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int line_search,
+                   const lbfgs_constants* k, const double* x0_host, double* x_out_host,
+                   int max_iterations, double tolerance, unsigned flags, lbfgs_result* out) {
+    return minimize_at(c, objective, cb, line_search, k, x0_host, x_out_host, 0, max_iterations, tolerance, flags,
+                       out);
+}
+
+int lbfgs_minimize_device(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int line_search,
+                          const lbfgs_constants* k, const double* x0_dev, double* x_out_dev,
+                          int max_iterations, double tolerance, unsigned flags, lbfgs_result* out) {
+    return minimize_at(c, objective, cb, line_search, k, x0_dev, x_out_dev, 1, max_iterations, tolerance, flags,
+                       out);
 }
 
 int lbfgs_messages(const lbfgs_ctx* c, char* buf, int cap) {

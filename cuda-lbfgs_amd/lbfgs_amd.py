@@ -16,12 +16,13 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LBFGS_LIB") or os.path.join(HERE, "liblbfgs_hip.so")  # LBFGS_LIB: A/B builds
 
-OBJECTIVES = {"rosenbrock": 0, "quad_tridiag": 1, "quad_sep": 2, "host": 3, "dense": 4}
+OBJECTIVES = {"rosenbrock": 0, "quad_tridiag": 1, "quad_sep": 2, "host": 3, "dense": 4, "device": 5}
 LINE_SEARCHES = {"backtracking": 0, "interpolation": 1, "wolfe": 2, "backtracking_wolfe": 3}
 STATUS = {0: "converged", 1: "max_iter", 2: "ls_failed", 3: "running"}
 FLAG_VERBOSE, FLAG_QUIET, FLAG_TRACE, FLAG_UNFUSED, FLAG_VECTOR_FREE = 1, 2, 4, 8, 16
 FLAG_REFERENCE_CALLS = 32
 FLAG_CUDA_COMPAT = 64
+DEVICE_EAGER_GRAD = 1  # lbfgs_device_fn.flags: every device-callback call asks for f and grad together
 FLAG_CUDA_VARIANT = 128  # LBFGS_CUDA's semantics (parallel-implementation/L-BFGS.cu), include/lbfgs_hip.h
 KERNELS = ["dot", "axpy_dot", "mid", "axpy2_dot", "last", "negdot", "eval", "trial_f",
            "trial_fg", "commit", "point", "checksum", "update", "vf_commit", "vf_dir", "small_iter",
@@ -65,6 +66,14 @@ HOST_G = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_doubl
 
 class HostFn(C.Structure):
     _fields_ = [("f", HOST_F), ("grad", HOST_G), ("user", C.c_void_p)]
+
+
+# int eval(const double* x_dev, int64_t n, double* f_out, double* g_dev, void* user)
+DEVICE_EVAL = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.c_void_p, C.c_void_p)
+
+
+class DeviceFn(C.Structure):
+    _fields_ = [("eval", DEVICE_EVAL), ("user", C.c_void_p), ("flags", C.c_uint)]
 
 
 _lib = None
@@ -156,6 +165,16 @@ def lib():
     L.lbfgs_batch_trace_len.argtypes = [vp, C.c_int]
     L.lbfgs_batch_trace_get.argtypes = [vp, C.c_int, dp, dp, dp, C.c_int]
     L.lbfgs_batch_events_get.argtypes = [vp, C.c_int, C.POINTER(BatchEvents)]
+    L.lbfgs_set_device_objective.argtypes = [vp, C.POINTER(DeviceFn)]
+    L.lbfgs_minimize_device.argtypes = [vp, C.c_int, C.POINTER(HostFn), C.c_int, C.POINTER(Constants),
+                                        vp, vp, C.c_int, C.c_double, C.c_uint, C.POINTER(Result)]
+    L.lbfgs_solver_init_device.argtypes = [vp, C.c_int, C.POINTER(HostFn), C.c_int, C.POINTER(Constants),
+                                           vp, C.c_double, C.c_uint]
+    L.lbfgs_get_x_device.argtypes = [vp, vp]
+    L.lbfgs_reducer_create.argtypes = [C.POINTER(vp), C.c_int64, C.c_int]
+    L.lbfgs_reducer_destroy.argtypes = [vp]
+    L.lbfgs_reducer_destroy.restype = None
+    L.lbfgs_reducer_dot.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -175,6 +194,8 @@ EXPORTED_SYMBOLS = [
     "lbfgs_batch_plan", "lbfgs_batch_create", "lbfgs_batch_destroy", "lbfgs_batch_last_error",
     "lbfgs_batch_set_launch", "lbfgs_batch_minimize", "lbfgs_batch_trace_len", "lbfgs_batch_trace_get",
     "lbfgs_batch_events_get",
+    "lbfgs_set_device_objective", "lbfgs_minimize_device", "lbfgs_solver_init_device", "lbfgs_get_x_device",
+    "lbfgs_reducer_create", "lbfgs_reducer_destroy", "lbfgs_reducer_dot",
 ]
 PEER_HANDLE_BYTES = 64
 BACKENDS = {0: "single", 1: "rccl", 2: "xgmi", 3: "host-group"}
@@ -383,6 +404,121 @@ class Batch:
         return ev.as_dict()
 
 
+class _DeviceView:
+    """n float64 at a device address, for torch.as_tensor(view, device=...): a zero-copy tensor over
+    memory the library owns (torch takes no ownership; the view is valid while the library says so)."""
+
+    def __init__(self, ptr, n):
+        # torch accepts writable views only; a read-only buffer (the callback's x) is one by contract
+        self.__cuda_array_interface__ = dict(shape=(int(n),), typestr="<f8", data=(int(ptr), False), version=2,
+                                             strides=None)
+
+
+def hip_runtimes():
+    """Paths of the HIP runtime copies mapped into this process."""
+    try:
+        with open("/proc/self/maps") as fp:
+            return sorted({ln.split()[-1] for ln in fp if "libamdhip64" in ln})
+    except OSError:
+        return []
+
+
+_torch_checked = False
+
+
+def _torch():
+    """torch, for the entry points that share device memory with it. A torch wheel brings its own copy
+    of the HIP runtime; device memory cannot be shared across two copies in one process (and the
+    second to initialise finds no GPU). liblbfgs_hip.so binds to torch's copy when torch is imported
+    before the library is loaded; the other order is an error here, not a crash later."""
+    global _torch_checked
+    import torch
+
+    if _torch_checked:
+        return torch
+    lib()
+    rt = hip_runtimes()
+    if len(rt) > 1:
+        raise LbfgsError("torch and liblbfgs_hip.so are on different copies of the HIP runtime (" + ", ".join(rt) +
+                         "): import torch before the first lbfgs_amd call loads the library, so that it binds "
+                         "to the runtime torch brought")
+    _torch_checked = True
+    return torch
+
+
+def _device_tensor(ptr, n, device):
+    import torch
+
+    return torch.as_tensor(_DeviceView(ptr, n), device=device)
+
+
+def _check_device_tensor(t, n, device, what):
+    torch = _torch()
+
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 1 and
+            t.numel() == n and t.is_contiguous() and (t.device.index or 0) == device):
+        raise ValueError(f"{what}: a contiguous float64 CUDA tensor of {n} elements on device {device} is required")
+
+
+class Reducer:
+    """The solver's canonical fixed-order reduction over CUDA tensors of n float64 (lbfgs_reducer_*):
+    dot(a, b) has the bits of Context.dot for the same data, sum(t) those of the dot with ones. For
+    device objectives (Context.set_device_objective) that reduce their per-element terms to f. The
+    tensors may sit at any storage offset; nothing outside them is read. Runs on torch's current
+    stream (the null stream orders nothing against the library's own non-blocking streams, so when
+    that is the current one it is synchronised first and the reducer's own stream is used); the
+    value is complete on return."""
+
+    def __init__(self, n, device=0):
+        _torch()
+        self.n, self.device = int(n), int(device)
+        h = C.c_void_p()
+        rc = lib().lbfgs_reducer_create(C.byref(h), self.n, self.device)
+        if rc != 0:
+            e = LbfgsError(f"lbfgs_reducer_create failed ({rc})")
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().lbfgs_reducer_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def dot(self, a, b=None):
+        torch = _torch()
+
+        _check_device_tensor(a, self.n, self.device, "Reducer: a")
+        if b is not None:
+            _check_device_tensor(b, self.n, self.device, "Reducer: b")
+        st = torch.cuda.current_stream(self.device)
+        if not st.cuda_stream:
+            st.synchronize()
+        out = C.c_double()
+        rc = lib().lbfgs_reducer_dot(self.h, a.data_ptr(), b.data_ptr() if b is not None else None,
+                                     st.cuda_stream or None, C.byref(out))
+        if rc != 0:
+            e = LbfgsError(f"lbfgs_reducer_dot failed ({rc})")
+            e.rc = rc
+            raise e
+        return out.value
+
+    def sum(self, t):
+        return self.dot(t, None)
+
+
 class Context:
     """A persistent solver context: device vectors for n (or this rank's shard of n) and the
     m-pair history ring stay resident across calls."""
@@ -403,6 +539,9 @@ class Context:
         lib().lbfgs_local_range(self.h, C.byref(lo), C.byref(nl))
         self.elem_lo, self.n_loc = lo.value, nl.value
         self._cb = None
+        self.device = int(device)
+        self._dev_cb = None   # keeps the device callback's ctypes thunk alive
+        self._dev_exc = None  # a Python exception raised inside it, re-raised by the calling method
 
     def close(self):
         if getattr(self, "h", None):
@@ -570,8 +709,127 @@ class Context:
         return lib().lbfgs_exchange_fold(self.h) == 1
 
     def _err(self, what, rc):
+        exc, self._dev_exc = self._dev_exc, None
+        if exc is not None:  # the device callback raised: the library saw a nonzero return
+            raise exc
         msg = lib().lbfgs_last_error(self.h)
-        raise LbfgsError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+        e = LbfgsError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+        e.rc = rc
+        raise e
+
+    # ---- device-callback objective, device-resident x0 / x ----
+    def set_device_objective(self, fn, eager_grad=False):
+        """The "device" objective: fn(x, want_grad) -> f, or (f, g) when want_grad. x is a float64 CUDA
+        tensor of n elements, a zero-copy view of solver memory, valid during the call and read-only
+        by contract; g is a tensor of n elements (copied into a zero-copy view of the solver's
+        gradient buffer); f a number or a one-element tensor. The solver's work on x is complete when
+        fn is called, so fn may read it on any torch stream; the glue copies g and then synchronises
+        on the stream that is current when fn has returned, so an fn that worked on a stream it
+        entered itself synchronises that one before it returns. eager_grad: every call asks for the gradient (for objectives
+        whose backward pass is cheap next to a second forward pass); the iterates are the same.
+        An exception raised by fn ends the solve and is re-raised by the method that ran it.
+        fn = None clears the objective."""
+        if fn is None:
+            rc = lib().lbfgs_set_device_objective(self.h, None)
+            self._dev_cb = None
+            if rc != 0:
+                self._err("lbfgs_set_device_objective", rc)
+            return
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+
+        def ev(xp, n, fp, gp, user):
+            try:
+                with torch.cuda.device(dev):
+                    x = _device_tensor(xp, n, dev)
+                    r = fn(x, bool(gp))
+                    f, g = (r if isinstance(r, (tuple, list)) else (r, None))
+                    if gp:
+                        if g is None:
+                            raise ValueError("device objective: a gradient was asked for, fn returned none")
+                        _device_tensor(gp, n, dev).copy_(torch.as_tensor(g, dtype=torch.float64, device=dev)
+                                                         .reshape(n))
+                    if fp:
+                        fp[0] = float(f)
+                    torch.cuda.current_stream(dev).synchronize()
+                return 0
+            except BaseException as e:  # never unwinds through the C frames
+                self._dev_exc = e
+                return 1
+
+        cb = DEVICE_EVAL(ev)
+        fnc = DeviceFn(cb, None, DEVICE_EAGER_GRAD if eager_grad else 0)
+        rc = lib().lbfgs_set_device_objective(self.h, C.byref(fnc))
+        if rc != 0:
+            self._err("lbfgs_set_device_objective", rc)
+        self._dev_cb = cb
+
+    def _flags(self, verbose=False, quiet=True, trace=False, unfused=False, vector_free=False,
+               reference_calls=False, cuda_compat=False, cuda_variant=False):
+        return (FLAG_VERBOSE if verbose else 0) | (FLAG_QUIET if quiet else 0) | \
+               (FLAG_TRACE if trace else 0) | (FLAG_UNFUSED if unfused else 0) | \
+               (FLAG_VECTOR_FREE if vector_free else 0) | (FLAG_REFERENCE_CALLS if reference_calls else 0) | \
+               (FLAG_CUDA_COMPAT if cuda_compat else 0) | (FLAG_CUDA_VARIANT if cuda_variant else 0)
+
+    def minimize_device(self, objective, x0, line_search="backtracking", max_iterations=1000, tolerance=1e-5,
+                        verbose=False, quiet=True, trace=False, consts=None, f=None, grad=None, unfused=False,
+                        vector_free=False, reference_calls=False, out=None, cuda_compat=False,
+                        cuda_variant=False):
+        """minimize() with x0 and the result in device memory: x0 and out are contiguous float64 CUDA
+        tensors of n elements (a slice at any storage offset is fine; out: a new tensor when None).
+        One rank, every objective. The result's "x" is the tensor; every number is bit for bit
+        minimize()'s, except passes / bytes, which also count the two copy passes."""
+        torch = _torch()
+
+        _check_device_tensor(x0, self.n, self.device, "minimize_device: x0")
+        if out is not None:
+            _check_device_tensor(out, self.n, self.device, "minimize_device: out")
+        x = out if out is not None else torch.empty(self.n, dtype=torch.float64, device=x0.device)
+        torch.cuda.current_stream(self.device).synchronize()  # the caller's work on x0 is complete
+        res = Result()
+        flags = self._flags(verbose, quiet, trace, unfused, vector_free, reference_calls, cuda_compat, cuda_variant)
+        cb = self._host_fn(f, grad) if objective == "host" else None
+        k = consts if consts is not None else constants("cuda" if cuda_compat else "config")
+        self._dev_exc = None
+        rc = lib().lbfgs_minimize_device(self.h, OBJECTIVES[objective], C.byref(cb) if cb else None,
+                                         LINE_SEARCHES[line_search], C.byref(k), x0.data_ptr(), x.data_ptr(),
+                                         int(max_iterations), float(tolerance), flags, C.byref(res))
+        if rc < 0:
+            self._err("lbfgs_minimize_device", rc)
+        r = res.as_dict()
+        r["x"] = x
+        r["messages"] = self.messages()
+        if trace:
+            r.update(self.trace())
+        return r
+
+    def init_device(self, objective, x0, line_search="backtracking", tolerance=1e-5, quiet=True, trace=False,
+                    consts=None, unfused=False, vector_free=False):
+        """init() with x0 a CUDA tensor (see minimize_device)."""
+        torch = _torch()
+
+        _check_device_tensor(x0, self.n, self.device, "init_device: x0")
+        torch.cuda.current_stream(self.device).synchronize()
+        flags = self._flags(quiet=quiet, trace=trace, unfused=unfused, vector_free=vector_free)
+        k = consts if consts is not None else constants()
+        self._dev_exc = None
+        rc = lib().lbfgs_solver_init_device(self.h, OBJECTIVES[objective], None, LINE_SEARCHES[line_search],
+                                            C.byref(k), x0.data_ptr(), float(tolerance), flags)
+        if rc != 0:
+            self._err("lbfgs_solver_init_device", rc)
+
+    def get_x_device(self, out=None):
+        """get_x() into a CUDA tensor (a new one when out is None); complete on return."""
+        torch = _torch()
+
+        if out is not None:
+            _check_device_tensor(out, self.n, self.device, "get_x_device: out")
+        x = out if out is not None else torch.empty(self.n, dtype=torch.float64,
+                                                    device=torch.device("cuda", self.device))
+        rc = lib().lbfgs_get_x_device(self.h, x.data_ptr())
+        if rc != 0:
+            self._err("lbfgs_get_x_device", rc)
+        return x
 
     def _host_fn(self, f, grad):
         def cf(xp, n, user):

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define LBFGS_HIP_ABI_VERSION 2
+#define LBFGS_HIP_ABI_VERSION 3
 
 typedef struct lbfgs_ctx lbfgs_ctx;
 
@@ -47,7 +47,8 @@ enum {
     LBFGS_OBJ_QUAD_TRIDIAG = 1,   /* generate_quadratic_function(n), benchmark.cpp:16-56 */
     LBFGS_OBJ_QUAD_SEPARABLE = 2, /* main.cpp:7-21 */
     LBFGS_OBJ_HOST = 3,           /* user callbacks (lbfgs_host_fn) */
-    LBFGS_OBJ_DENSE_QUAD = 4      /* f = x'Ax + b'x on the device (lbfgs_set_dense_quadratic) */
+    LBFGS_OBJ_DENSE_QUAD = 4,     /* f = x'Ax + b'x on the device (lbfgs_set_dense_quadratic) */
+    LBFGS_OBJ_DEVICE = 5          /* user callback on device memory (lbfgs_set_device_objective) */
 };
 
 /* line searches, lbfgs.cpp:40-70 */
@@ -149,6 +150,30 @@ typedef struct {
     void* user;
 } lbfgs_host_fn;
 
+/* Device-callback objective (LBFGS_OBJ_DEVICE): the caller's objective evaluated where the solver's
+ * vectors live, nothing crossing to the host but f. One rank.
+ * x_dev: n doubles of solver-owned device memory, read-only, valid during the call.
+ * f_out != NULL: store f(x) there (host double). g_dev != NULL: store grad f(x) into g_dev[0..n)
+ * (solver-owned device memory; nothing outside [0, n) may be written). Either may be NULL, not both.
+ * Return 0; anything else ends the solve with LBFGS_ERR_CALLBACK.
+ * Ordering: when eval is entered, every solver launch that produced x_dev has completed (the solver
+ * stream is synchronised first). When eval returns, the work that wrote g_dev must be complete: the
+ * callback synchronises its own stream. The solver stream is non-blocking, so work queued on the
+ * null stream is ordered against nothing of the solver's.
+ * By default f and grad are asked for as the host-callback path asks (one f and at most one grad
+ * call per distinct point; a gradient wanted where f is not known yet asks for both).
+ * LBFGS_DEVICE_EAGER_GRAD: every call asks for f and grad together and the gradient is kept for the
+ * point, for objectives whose backward pass is cheap next to a second forward pass. The iterates
+ * are bit-identical either way; lbfgs_result's f_calls / grad_calls count the calls that carried
+ * f_out / g_dev. */
+typedef int (*lbfgs_device_eval)(const double* x_dev, int64_t n, double* f_out, double* g_dev, void* user);
+#define LBFGS_DEVICE_EAGER_GRAD 1u
+typedef struct {
+    lbfgs_device_eval eval;
+    void* user;
+    unsigned flags;
+} lbfgs_device_fn;
+
 typedef struct {
     int iterations;      /* iterations performed (k at exit) */
     int status;          /* LBFGS_STATUS_* */
@@ -162,9 +187,16 @@ typedef struct {
     double seconds;      /* wall time of the solve / step call */
     int h_min, h_max;    /* history pairs stored at the top of the iterations this call ran
                           * (h of SURVEY.md 8(d)'s B_iter; -1 when the call ran none) */
-    int64_t f_calls;     /* host-callback objective: f / grad callbacks since solver init */
+    int64_t f_calls;     /* host- / device-callback objective: f / grad callbacks since solver init */
     int64_t grad_calls;
 } lbfgs_result;
+
+/* Sets (fn == NULL: clears) the context's device-callback objective; lbfgs_minimize and
+ * lbfgs_solver_init (and their _device forms) then take objective = LBFGS_OBJ_DEVICE with cb = NULL.
+ * LBFGS_ERR_BAD_ARG from those when none is set, on a sharded context, or with LBFGS_FLAG_UNFUSED,
+ * _VECTOR_FREE, _REFERENCE_CALLS or _CUDA_COMPAT; lbfgs_line_search, lbfgs_dev_objective and
+ * lbfgs_dev_trial do not take it. */
+int lbfgs_set_device_objective(lbfgs_ctx* ctx, const lbfgs_device_fn* fn);
 
 /* "src=<16 hex digits of sha256 over the library's sources> built=<date time> arch=gfx950":
  * identifies the sources a loaded library was built from (build provenance) */
@@ -319,6 +351,20 @@ int lbfgs_solver_step(lbfgs_ctx* ctx, int max_steps, lbfgs_result* out);
 int lbfgs_get_x(lbfgs_ctx* ctx, double* x_out_host);
 int lbfgs_sync(lbfgs_ctx* ctx);
 
+/* The same with x0 and x in device memory (one rank, any objective; else LBFGS_ERR_BAD_ARG):
+ * x0_dev / x_out_dev are n doubles on the context's device, caller-owned, unpadded, 8-byte aligned
+ * and no more. The caller's work on x0_dev is complete at the call; x_out_dev is complete on return.
+ * Each is copied to or from the solver's own vector by one bounds-guarded kernel pass on the solver
+ * stream (counted in lbfgs_result's passes and bytes): no solver pass ever runs on a caller's
+ * buffer. Iterates, f, |g|, trace and messages are bit for bit those of the host-buffer forms. */
+int lbfgs_minimize_device(lbfgs_ctx* ctx, int objective, const lbfgs_host_fn* cb, int line_search,
+                          const lbfgs_constants* k, const double* x0_dev, double* x_out_dev,
+                          int max_iterations, double tolerance, unsigned flags, lbfgs_result* out);
+int lbfgs_solver_init_device(lbfgs_ctx* ctx, int objective, const lbfgs_host_fn* cb, int line_search,
+                             const lbfgs_constants* k, const double* x0_dev, double tolerance,
+                             unsigned flags);
+int lbfgs_get_x_device(lbfgs_ctx* ctx, double* x_out_dev);
+
 /* messages printed by the last solve (the reference's stdout lines), NUL-terminated */
 int lbfgs_messages(const lbfgs_ctx* ctx, char* buf, int cap);
 /* per-iteration trace (LBFGS_FLAG_TRACE): entry k = state at the top of iteration k */
@@ -371,6 +417,20 @@ int lbfgs_batch_trace_get(const lbfgs_batch* b, int problem, double* f, double* 
  * "Skipping update", "Invalid rho", "Invalid gamma" (a failed line search is the status) */
 typedef struct { int not_descent, skipped_updates, invalid_rho, invalid_gamma; } lbfgs_batch_events;
 int lbfgs_batch_events_get(const lbfgs_batch* b, int problem, lbfgs_batch_events* out);
+
+/* ---- canonical reductions on caller-owned device buffers -------------------------------- */
+/* For objectives evaluated on the device (LBFGS_OBJ_DEVICE): the sum of their per-element terms in
+ * the solver's canonical fixed order, so that f is reproducible run to run and
+ * comparable bit for bit with lbfgs_dev_dot. The buffers are n doubles of caller-owned device
+ * memory, unpadded, 8-byte aligned and no more; nothing outside [0, n) is read. */
+typedef struct lbfgs_reducer lbfgs_reducer;
+int lbfgs_reducer_create(lbfgs_reducer** out, int64_t n, int device);
+void lbfgs_reducer_destroy(lbfgs_reducer* r);
+/* canonical fixed-order sum of a_i * b_i (b_dev == NULL: of a_i) over caller-owned device buffers
+ * of n doubles; launched on hip_stream (a hipStream_t, NULL = the reducer's own); *out_host is
+ * valid on return */
+int lbfgs_reducer_dot(lbfgs_reducer* r, const double* a_dev, const double* b_dev, void* hip_stream,
+                      double* out_host);
 
 /* ---- line search alone (line_search.h:10-26 on the GPU) -------------------------------- */
 /* Step size along d from x (gradient g at x) by one of the four line searches, every trial on
