@@ -45,11 +45,7 @@ int lbk_vf_factor(int64_t n) {
     int64_t L = ((per + 127) / 128) * 128;
     if (L < 512) L = 512;
     int F = 1;
-#ifdef LBK_VF_FMAX  // experiments: cap the factor (1 = the original vector-free geometry)
-    const int fmax = LBK_VF_FMAX;
-#else
-    const int fmax = 8;
-#endif
+    const int fmax = 8;  // the cap (1 would be the original vector-free geometry)
     while (F < fmax && 2 * F * L <= 8192 && (n + 2 * F * L - 1) / (2 * F * L) >= 1024) F *= 2;
     return F;
 }
@@ -70,9 +66,6 @@ int lbk_geometry_plan(int64_t n, int rank, int world, lbk_geo* out) {
     // oracle's orc_canon_geometry states the rule.
     const int64_t lmin = (n >= LBK_MIDL_LO && n <= LBK_MIDL_HI) ? LBK_MIDL : 512;
     if (G.L < lmin) G.L = lmin;
-#ifdef LBK_DEBUG_SEGLEN  // timing experiments only (tools/gpu_ab_shardgeo.sh): breaks the canonical order
-    G.L = LBK_DEBUG_SEGLEN;
-#endif
     G.nseg = (n + G.L - 1) / G.L;
     G.rank = rank;
     G.world = world;
@@ -114,7 +107,7 @@ int lbk_create(lbk_ctx** out, int device, int64_t n, int rank, int world, const 
     // front pad 32 doubles: ghost at [-1] and element 0 on a 256-B boundary, so every 1-KiB
     // row load/store covers whole cache lines; back: whole rows + halo
     // non-temporal streaming of the history (the work vectors q/r/d keep the temporal policy,
-    // LBK_WORK_TEMPORAL) once vectors no longer fit comfortably in the 256 MiB Infinity Cache.
+    // ldw / st2w) once vectors no longer fit comfortably in the 256 MiB Infinity Cache.
     // Two-loop passes: -2 % at n_loc = 1e7, +1.3 % at 1.25e7, +4 % at 1e8; vector-free passes
     // (2m+6 vectors each): +1.5 % at 2e6, +5 % at 1e7 and above (profiles/r01/nt_threshold_ab.txt,
     // work_temporal_ab.txt). Override for both: LBFGS_NT=0/1
@@ -221,26 +214,16 @@ int lbk_create(lbk_ctx** out, int device, int64_t n, int rank, int world, const 
     // take across GPUs.
     c->cu_part = 0;
     if (const char* e = getenv("LBFGS_CU_PARTITION")) c->cu_part = world > 1 && !grp && atoi(e) != 0;
-    int pworld = world, prank = rank;
-#ifdef LBK_DEBUG_CU_WORLD  // timing experiments only (variant builds): a one-rank context confined to
-    // rank LBFGS_DEBUG_CU_RANK's (default 0) CU share of a LBK_DEBUG_CU_WORLD-rank partition
-    if (world == 1 && !grp) {
-        c->cu_part = 1;
-        pworld = LBK_DEBUG_CU_WORLD;
-        prank = 0;
-        if (const char* e = getenv("LBFGS_DEBUG_CU_RANK")) prank = atoi(e) % LBK_DEBUG_CU_WORLD;
-    }
-#endif
     if (c->cu_part) {
         int cus = 0;
         CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        const int per = cus / pworld;
+        const int per = cus / world;
         if (per < 1) {
-            snprintf(c->err, sizeof c->err, "LBFGS_CU_PARTITION: %d CUs cannot be split over %d ranks", cus, pworld);
+            snprintf(c->err, sizeof c->err, "LBFGS_CU_PARTITION: %d CUs cannot be split over %d ranks", cus, world);
             return -1;
         }
         std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0u);
-        for (int i = prank * per; i < (prank + 1) * per; ++i) mask[(size_t)i >> 5] |= 1u << (i & 31);
+        for (int i = rank * per; i < (rank + 1) * per; ++i) mask[(size_t)i >> 5] |= 1u << (i & 31);
         CK(hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)mask.size(), mask.data()));
         std::vector<uint32_t> got(mask.size(), 0u);
         CK(hipExtStreamGetCUMask(c->stream, (uint32_t)got.size(), got.data()));
@@ -336,7 +319,7 @@ int lbk_create(lbk_ctx** out, int device, int64_t n, int rank, int world, const 
         SEARCH_OCC(LBK_OBJ_QUAD_SEPARABLE)
 #undef SEARCH_OCC
         c->wolfe_max = (int)std::min<int64_t>(c->coop_max, (int64_t)wocc * cus);
-        // the persistent forms: every workgroup of their grid resident, at most `cap` per CU (the
+        // the persistent two-loop: every workgroup of its grid resident, at most `cap` per CU (the
         // occupancy answer is VGPR-bound here, where the API and the hardware agree;
         // MI355X_MICROARCH.md's one-short case is SGPR-bound, 82-98 SGPRs at 7-8 per CU). A grid that
         // does not fit still ends: every flagged wait times out (2 s).
@@ -346,71 +329,27 @@ int lbk_create(lbk_ctx** out, int device, int64_t n, int rank, int world, const 
         // queries use the same figure
         int lds_cu = 0;
         CK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device));
-        // (an A/B without the reservation changed nothing: -DLBK_PERSIST_LDS=0 in variant builds)
-#ifdef LBK_PERSIST_LDS
-        const int lds_on = LBK_PERSIST_LDS;
-#else
-        const int lds_on = 1;
-#endif
-        c->persist_lds = lds_on && lds_cu > 0 ? lds_cu / (cap + 1) + 1024 : 0;
-        c->persist_gmax = 0;
-#if LBK_PERSIST_ITER
-        // the whole iteration (LBFGS_PERSIST=1, variant builds only; 165 VGPRs: 3 per CU)
-        int po = 1 << 30;
-        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (k_persist_iter<LBK_OBJ_ROSENBROCK, true>), LB_BLOCK, c->persist_lds));
-        po = std::min(po, o);
-        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (k_persist_iter<LBK_OBJ_QUAD_TRIDIAG, true>), LB_BLOCK, c->persist_lds));
-        po = std::min(po, o);
-        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (k_persist_iter<LBK_OBJ_QUAD_SEPARABLE, true>), LB_BLOCK, c->persist_lds));
-        po = std::min(po, o);
-        c->persist_gmax = std::min(po, cap) * cus;
-#else
-        int po = 0;
-#endif
-        // the persistent two-loop (LBFGS_PERSIST=2) without the commit's registers; its LDS
-        // reservation lets exactly `cap` workgroups onto a CU, so the dispatcher spreads the resident
-        // grid evenly (without it two workgroups can share a CU while another idles; A/B
-        // LBFGS_PERSIST_LDS=0). A kernel the reservation cannot be granted to turns the mode off.
+        // The LDS reservation lets exactly `cap` workgroups onto a CU, so the dispatcher spreads the
+        // resident grid evenly (without it two workgroups can share a CU while another idles; a
+        // build without the reservation measured no different and was removed). A kernel the
+        // reservation cannot be granted to turns the mode off.
+        c->persist_lds = lds_cu > 0 ? lds_cu / (cap + 1) + 1024 : 0;
         bool lds_ok = true;
         if (c->persist_lds) {
             lds_ok &= hipFuncSetAttribute((const void*)k_persist_twoloop<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           c->persist_lds) == hipSuccess;
             lds_ok &= hipFuncSetAttribute((const void*)k_persist_twoloop<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           c->persist_lds) == hipSuccess;
-#if LBK_PERSIST_ITER
-#define PSET(O)                                                                                                            \
-    lds_ok &= hipFuncSetAttribute((const void*)k_persist_iter<O, true>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                  c->persist_lds) == hipSuccess;                                                           \
-    lds_ok &= hipFuncSetAttribute((const void*)k_persist_iter<O, false>, hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                                  c->persist_lds) == hipSuccess
-            PSET(LBK_OBJ_ROSENBROCK);
-            PSET(LBK_OBJ_QUAD_TRIDIAG);
-            PSET(LBK_OBJ_QUAD_SEPARABLE);
-#undef PSET
-#endif
             (void)hipGetLastError();
         }
         CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_persist_twoloop<true>, LB_BLOCK, c->persist_lds));
-        po = o;
+        int po = o;
         CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_persist_twoloop<false>, LB_BLOCK, c->persist_lds));
         po = std::min(po, o);
         c->persist2_gmax = lds_ok ? std::min(po, cap) * cus : 0;
-        if (!lds_ok) c->persist_gmax = 0;
     }
     c->persist_on = 0;
-    if (const char* e = getenv("LBFGS_PERSIST")) c->persist_on = atoi(e);  // 1: whole iteration, 2: two-loop
-    // strided segment ownership and walks without the alternation measured slower:
-    // variant builds only (-DLBK_PERSIST_STRIDE=1, -DLBK_PERSIST_ALT=0)
-#ifdef LBK_PERSIST_STRIDE
-    c->persist_stride = LBK_PERSIST_STRIDE;
-#else
-    c->persist_stride = 0;
-#endif
-#ifdef LBK_PERSIST_ALT
-    c->persist_alt = LBK_PERSIST_ALT;
-#else
-    c->persist_alt = 1;
-#endif
+    if (const char* e = getenv("LBFGS_PERSIST")) c->persist_on = atoi(e);  // 2: the persistent two-loop; any other value: off
     CK(hipMalloc(&c->fold_wait, sizeof(unsigned long long)));
     CK(hipMemset(c->fold_wait, 0, sizeof(unsigned long long)));
     CK(hipMalloc(&c->persist_cnt, sizeof(unsigned long long) * LBK_GROUPS));
@@ -1057,25 +996,25 @@ int lbk_elementwise(lbk_ctx* c, int op, double* out, const double* a, const doub
     });
 }
 
-// ---- vector-free mode -------------------------------------------------------------------
-// the persistent iteration's segments per workgroup (1..16, dividing a group's 1024) for this n,
-// or 0 when it is off or the grid would not be resident
-// the persistent forms' grid (resident workgroups, each owning every G-th segment) when `mode` is
-// on for this context, else 0
-static int persist_grid(const lbk_ctx* c, int mode, int gmax) {
-    if (c->persist_on != mode || c->geo.world != 1 || c->comm || !c->direct || c->geo.nseg <= c->coop_max) return 0;
-    return (int)std::min<int64_t>(gmax, c->geo.nseg);
+// the persistent two-loop's grid (resident workgroups, each owning a chunk of ceil(nseg / grid)
+// consecutive segments) when LBFGS_PERSIST=2 is on for this context, else 0
+static int persist_grid(const lbk_ctx* c) {
+    if (c->persist_on != 2 || c->geo.world != 1 || c->comm || !c->direct || c->geo.nseg <= c->coop_max) return 0;
+    const int64_t grid = std::min<int64_t>(c->persist2_gmax, c->geo.nseg);
+    if (grid < 1) return 0;
+    // persist_pass keeps one row of LDS per owned segment (segp, kPersistSegMax rows): a longer
+    // chunk leaves the launch sequence in charge, which gives the same bits. One rank has at most
+    // LBK_SEGS = 8192 segments, so this takes a device whose resident grid is below 128 workgroups.
+    if ((c->geo.nseg + grid - 1) / grid > kPersistSegMax) return 0;
+    return (int)grid;
 }
-static int persist_fits(const lbk_ctx* c) { return persist_grid(c, 1, c->persist_gmax); }
 
-int lbk_twoloop_ok(const lbk_ctx* c, int h) {
-    return h >= 1 && h <= LBK_SMALL_HMAX && persist_grid(c, 2, c->persist2_gmax) > 0;
-}
+int lbk_twoloop_ok(const lbk_ctx* c, int h) { return h >= 1 && h <= LBK_SMALL_HMAX && persist_grid(c) > 0; }
 
 int lbk_twoloop_persist(lbk_ctx* c, int h, const double* g, double* q, double* r, const double* const* S,
                         const double* const* Y, const double* rho, double gamma, int p0_ref, int slot_p0,
                         int slot_a0, int slot_b0) {
-    const int nb = lbk_twoloop_ok(c, h) ? persist_grid(c, 2, c->persist2_gmax) : 0;
+    const int nb = lbk_twoloop_ok(c, h) ? persist_grid(c) : 0;
     if (!nb) return -1;
     // p0_ref's slot is read directly (slot_total) by the kernel: a stage 2 still pending for it
     // (deferred, or a folded exchange) must land first
@@ -1108,15 +1047,13 @@ int lbk_twoloop_persist(lbk_ctx* c, int h, const double* g, double* q, double* r
     a.slot_p0 = slot_p0;
     a.slot_a0 = slot_a0;
     a.slot_b0 = slot_b0;
-    a.ll = c->coop_ll;
     a.seq_base = (unsigned)c->coop_base;
     a.err = c->coop_err_d;
     a.timeout = (unsigned long long)(2.0 * c->wall_khz * 1e3);  // 2 s: a grid that is not resident ends
     a.partials = c->partials;
     a.pcnt = c->persist_cnt;
     a.gflag = c->persist_gflag;
-    a.spw = c->persist_stride ? 0 : (c->geo.nseg + nb - 1) / nb;
-    a.alt = c->persist_alt;
+    a.spw = (c->geo.nseg + nb - 1) / nb;
     c->coop_base += (unsigned long long)((p0_ref >= 0 ? 0 : 1) + 2 * h - 1);
     Geo geo = kgeo(c);
     geo.rev = 0;
@@ -1169,74 +1106,52 @@ int lbk_small_iter(lbk_ctx* c, int obj, int h, const double* g, double* q, doubl
     // algorithmic bytes: the multi-launch sequence's passes (P0 dot if computed, 4 per pair
     // pass, 3 for mid, 8 for the commit)
     const double vec = (p0_ref >= 0 ? 0.0 : 2.0) + 4.0 * (h - 1) + 3.0 + 4.0 * (h - 1) + 8.0;
-    const int persist = persist_fits(c);
-    if ((c->coop_max > 0 && c->geo.nseg <= c->coop_max) || persist) {
-        // passes of this launch (sequence numbers it tags): [P0] + (h-1) first-loop + mid + (h-1)
-        // second-loop + commit
-        const int passes = (p0_ref >= 0 ? 0 : 1) + 2 * h;
-        a.ll = c->coop_ll;
-        a.seq_base = (unsigned)c->coop_base;
-        a.err = c->coop_err_d;
-        a.timeout = (unsigned long long)(2.0 * c->wall_khz * 1e3);  // 2 s
-        if (c->direct) {  // a completion record the host can wait on without a stream sync
-            const unsigned long long e = ++c->sp_epoch;
-            const int i = (int)(e & 3);
-            a.epoch = e;
-            a.done = c->sp_dh;
-            a.rec = c->sp_dh + 4 + 4 * i;
-            c->sp_base[i] = c->coop_base;
-            c->sp_bytes[i] = vec * 8.0 * (double)c->geo.n_loc;
-            c->sp_spec[i] = spec != nullptr;
-            if (spec) {
-                a.spec = 1;
-                a.spec_ls = spec->ls;
-                a.prev_c = c->slots + (int64_t)spec->prev_slot * LBK_SLOT;
-                a.spec_fx = spec->fx;
-                a.spec_c1 = spec->c1;
-                a.spec_c2 = spec->c2;
-                a.spec_tol = spec->tol;
-                a.vd = c->sp_vd + i;
-                if (spec->chain_epoch) {
-                    a.chain = c->sp_vd + (spec->chain_epoch & 3);
-                    a.chain_want = (spec->chain_epoch << 1) | 1ull;
-                }
+    // passes of this launch (sequence numbers it tags): [P0] + (h-1) first-loop + mid + (h-1)
+    // second-loop + commit
+    const int passes = (p0_ref >= 0 ? 0 : 1) + 2 * h;
+    a.ll = c->coop_ll;
+    a.seq_base = (unsigned)c->coop_base;
+    a.err = c->coop_err_d;
+    a.timeout = (unsigned long long)(2.0 * c->wall_khz * 1e3);  // 2 s
+    if (c->direct) {  // a completion record the host can wait on without a stream sync
+        const unsigned long long e = ++c->sp_epoch;
+        const int i = (int)(e & 3);
+        a.epoch = e;
+        a.done = c->sp_dh;
+        a.rec = c->sp_dh + 4 + 4 * i;
+        c->sp_base[i] = c->coop_base;
+        c->sp_bytes[i] = vec * 8.0 * (double)c->geo.n_loc;
+        c->sp_spec[i] = spec != nullptr;
+        if (spec) {
+            a.spec = 1;
+            a.spec_ls = spec->ls;
+            a.prev_c = c->slots + (int64_t)spec->prev_slot * LBK_SLOT;
+            a.spec_fx = spec->fx;
+            a.spec_c1 = spec->c1;
+            a.spec_c2 = spec->c2;
+            a.spec_tol = spec->tol;
+            a.vd = c->sp_vd + i;
+            if (spec->chain_epoch) {
+                a.chain = c->sp_vd + (spec->chain_epoch & 3);
+                a.chain_want = (spec->chain_epoch << 1) | 1ull;
             }
-            if (epoch) *epoch = e;
         }
-        c->coop_base += (unsigned long long)passes;
-        geo.rev = 0;
-#if LBK_PERSIST_ITER
-        if (persist) {
-            a.partials = c->partials;
-            a.pcnt = c->persist_cnt;
-            a.gflag = c->persist_gflag;
-            const int nb = persist;
-            a.spw = c->persist_stride ? 0 : (c->geo.nseg + nb - 1) / nb;
-            a.alt = c->persist_alt;
-            return launch(c, LBK_K_SMALL_ITER, vec, -1, [&] {
-                NT_DISPATCH(c, switch (obj) {
-                    case LBK_OBJ_ROSENBROCK: hipLaunchKernelGGL((k_persist_iter<LBK_OBJ_ROSENBROCK, NT_>), dim3(nb), dim3(LB_BLOCK), c->persist_lds, c->stream, a, geo); break;
-                    case LBK_OBJ_QUAD_TRIDIAG: hipLaunchKernelGGL((k_persist_iter<LBK_OBJ_QUAD_TRIDIAG, NT_>), dim3(nb), dim3(LB_BLOCK), c->persist_lds, c->stream, a, geo); break;
-                    default: hipLaunchKernelGGL((k_persist_iter<LBK_OBJ_QUAD_SEPARABLE, NT_>), dim3(nb), dim3(LB_BLOCK), c->persist_lds, c->stream, a, geo); break;
-                });
-            });
-        }
-#endif
-        const int nb = (int)c->geo.nseg;
-        return launch(c, LBK_K_SMALL_ITER, vec, -1, [&] {
-            switch (obj) {
-                case LBK_OBJ_ROSENBROCK: hipLaunchKernelGGL(k_coop_iter<LBK_OBJ_ROSENBROCK>, dim3(nb), dim3(LB_BLOCK), 0, c->stream, a, geo); break;
-                case LBK_OBJ_QUAD_TRIDIAG: hipLaunchKernelGGL(k_coop_iter<LBK_OBJ_QUAD_TRIDIAG>, dim3(nb), dim3(LB_BLOCK), 0, c->stream, a, geo); break;
-                default: hipLaunchKernelGGL(k_coop_iter<LBK_OBJ_QUAD_SEPARABLE>, dim3(nb), dim3(LB_BLOCK), 0, c->stream, a, geo); break;
-            }
-        });
+        if (epoch) *epoch = e;
     }
-    snprintf(c->err, sizeof c->err, "lbk_small_iter: no one-launch form for this size");
-    return -1;
+    c->coop_base += (unsigned long long)passes;
+    geo.rev = 0;
+    const int nb = (int)c->geo.nseg;
+    return launch(c, LBK_K_SMALL_ITER, vec, -1, [&] {
+        switch (obj) {
+            case LBK_OBJ_ROSENBROCK: hipLaunchKernelGGL(k_coop_iter<LBK_OBJ_ROSENBROCK>, dim3(nb), dim3(LB_BLOCK), 0, c->stream, a, geo); break;
+            case LBK_OBJ_QUAD_TRIDIAG: hipLaunchKernelGGL(k_coop_iter<LBK_OBJ_QUAD_TRIDIAG>, dim3(nb), dim3(LB_BLOCK), 0, c->stream, a, geo); break;
+            default: hipLaunchKernelGGL(k_coop_iter<LBK_OBJ_QUAD_SEPARABLE>, dim3(nb), dim3(LB_BLOCK), 0, c->stream, a, geo); break;
+        }
+    });
 }
 
 int lbk_small_spec_ok(const lbk_ctx* c, int h) {
-    return lbk_small_ok(c, h) && c->direct && c->coop_max > 0 && c->geo.nseg <= c->coop_max;
+    return lbk_small_ok(c, h) && c->direct;
 }
 
 int lbk_search_dev_ok(const lbk_ctx* c, int obj) {
@@ -1459,8 +1374,7 @@ int lbk_fetch_marked(lbk_ctx* c, int slot, int ncomp, double* totals) {
 
 int lbk_small_ok(const lbk_ctx* c, int h) {
     if (c->geo.world != 1 || c->comm || h < 1 || h > LBK_SMALL_HMAX) return 0;
-    if (c->coop_max > 0 && c->geo.nseg <= c->coop_max) return 1;
-    return persist_fits(c) ? 1 : 0;
+    return c->coop_max > 0 && c->geo.nseg <= c->coop_max;
 }
 
 int lbk_update(lbk_ctx* c, int op, double* out, const double* a, const double* b, double rho, int slot_a,

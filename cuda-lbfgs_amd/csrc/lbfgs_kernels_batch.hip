@@ -67,15 +67,6 @@ struct BatchLds {
     BatchWave wv[4];
 };
 
-#ifndef LBK_BATCH_WAVES
-#define LBK_BATCH_WAVES 0  // A/B: > 0 asks the register allocation for that many waves per SIMD
-#endif
-#if LBK_BATCH_WAVES > 0
-#define LBK_BATCH_ATTR __attribute__((amdgpu_waves_per_eu(LBK_BATCH_WAVES)))
-#else
-#define LBK_BATCH_ATTR
-#endif
-
 // One pass of one problem: the segments in order, each exactly as its workgroup of the launch
 // sequence streams it; then the fixed-order total (coop_pass's nseg <= 64 form). The barrier with
 // its workgroup-scope fences also orders this pass's vector stores before the next pass's loads
@@ -130,7 +121,7 @@ __device__ __forceinline__ void batch_commit(const Geo& geo, BatchLds& L, const 
 }
 
 template <int OBJ, int LS>
-__global__ __launch_bounds__(LB_BLOCK) LBK_BATCH_ATTR void k_batch_solve(BatchArgs a, Geo geo) {
+__global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) {
     __shared__ BatchLds L;
     constexpr bool FG = LS == 2 || LS == 3;
     constexpr bool CAND = LS == 0;  // the backtracking search's second step rides the first commit

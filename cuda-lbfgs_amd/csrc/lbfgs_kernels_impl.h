@@ -149,27 +149,12 @@ __device__ __forceinline__ void st2m(double* p, double2 v, bool v0, bool v1) {
     }
 }
 
-// Work vectors (q / r / d: rewritten pass after pass, read again by the next) may keep the
-// temporal policy under NT so that, at per-rank sizes a few times below the Infinity Cache, they
-// stay resident while the history streams past (A/B variant: LBK_WORK_TEMPORAL).
-#ifndef LBK_WORK_TEMPORAL
-#define LBK_WORK_TEMPORAL 1
-#endif
-// A/B levels: 0 all NT; 1 q/r/d temporal; 2 + x, g; 3 + new s, y; 4 / 5 q/r/d loads / stores only
-#define LBK_WLD_T (LBK_WORK_TEMPORAL >= 1 && LBK_WORK_TEMPORAL <= 4)
-#define LBK_WST_T (LBK_WORK_TEMPORAL >= 1 && LBK_WORK_TEMPORAL != 4)
-#define LBK_XG_T (LBK_WORK_TEMPORAL == 2 || LBK_WORK_TEMPORAL == 3)
-#define LBK_SY_T (LBK_WORK_TEMPORAL == 3)
-template <bool NT>
-__device__ __forceinline__ double2 ldw(const double* p) {
-    return ldv<NT && !LBK_WLD_T>(p);
-}
-// level 2: the iterate and gradient (x, g; read by the trials, the last second-loop pass and
-// the commit) as well
-template <bool NT>
-__device__ __forceinline__ double2 ldx(const double* p) {
-    return ldv<NT && !LBK_XG_T>(p);
-}
+// Work vectors (q / r / d: rewritten pass after pass, read again by the next) keep the temporal
+// policy under NT so that, at per-rank sizes a few times below the Infinity Cache, they stay
+// resident while the history streams past: ldw here, st2w below. Everything else (x, g, the
+// history and the new s, y) follows NT. The other splits (all NT; x, g and the new pair temporal
+// as well; loads or stores only) were measured and removed.
+__device__ __forceinline__ double2 ldw(const double* p) { return ldv<false>(p); }
 
 // fixed-order total of the 8 group partials of one slot component
 __device__ __forceinline__ double slot_total(const double* p) {
@@ -197,7 +182,7 @@ __device__ __forceinline__ double bitsd(unsigned long long u) {
 // store is single-copy atomic, so a reader that sees both tags has both halves: no separate
 // arrival counter, no drain between the data and the flag. Agent-scope (sc1) stores and loads,
 // coherent across the XCDs' L2s.
-#define LBK_LL_SEGS 8192  // >= LBK_COOP_SEGMAX; every segment for the persistent iteration (LBFGS_PERSIST)
+#define LBK_LL_SEGS 8192  // >= LBK_COOP_SEGMAX: the stride of a component (every segment of one rank)
 #define LBK_LL_COMPS 10   // up to 8 reduction components + the 2 edge values of an r pass
 __device__ __forceinline__ void ll_store(unsigned long long* p, double v, unsigned seq) {
     const unsigned long long u = dbits(v), tag = (unsigned long long)seq << 32;
@@ -764,9 +749,10 @@ __device__ __forceinline__ void rows(const Op& op, const Seg& s, int u0, double 
     }
 }
 
-// Software-pipelined full-segment walk: the loads of row group k+1 are issued before group k is
-// computed and stored. The in-place passes (q, r) carry no __restrict__ between input and output,
-// so the compiler cannot hoist the next group's loads above this group's stores by itself.
+// The two halves of rows<false, UN> on their own, for a walk that issues a group's loads ahead of
+// something else (run_pass_prefetch: ahead of the poll for the folded scalar). A software-pipelined
+// full-segment walk built on them (group k+1's loads before group k's stores) was measured and removed
+// (DESIGN.md §4).
 template <int UN, int K, class Op>
 __device__ __forceinline__ void load_group(const Op& op, const Seg& s, int u0, typename Op::Row (&r)[UN]) {
 #pragma unroll
@@ -782,40 +768,10 @@ __device__ __forceinline__ void apply_group(const Op& op, const Seg& s, int u0, 
     }
 }
 
-template <int K, class Op>
-__device__ __forceinline__ void stream_pipelined(const Op& op, const Seg& s, double (&acc)[K]) {
-    constexpr int G = 2;  // rows per group
-    int u0 = 0;
-    if (s.nrows >= 2 * G) {
-        typename Op::Row a[G], b[G];
-        load_group<G, K>(op, s, 0, a);
-        for (;;) {
-            const bool more_b = u0 + 2 * G <= s.nrows;
-            if (more_b) load_group<G, K>(op, s, u0 + G, b);
-            apply_group<G, K>(op, s, u0, a, acc);
-            u0 += G;
-            if (!more_b) break;
-            const bool more_a = u0 + 2 * G <= s.nrows;
-            if (more_a) load_group<G, K>(op, s, u0 + G, a);
-            apply_group<G, K>(op, s, u0, b, acc);
-            u0 += G;
-            if (!more_a) break;
-        }
-    }
-    for (; u0 < s.nrows; ++u0) rows<false, 1>(op, s, u0, acc);
-}
-
-#ifndef LBK_PIPELINE
-#define LBK_PIPELINE 0
-#endif
-
 // Rows per load group on full segments. A pass with few load streams per row (k_mid: q and y0)
 // keeps fewer bytes in flight per wave at 4 rows; op_unroll widens its groups. The groups only
 // decide when loads are issued: rows are still applied, and accumulated, in ascending order, so
 // every unroll gives the same bits.
-#ifndef LBK_MID_UNROLL
-#define LBK_MID_UNROLL 8
-#endif
 template <class Op>
 struct op_unroll {
     static constexpr int value = 4;
@@ -824,15 +780,11 @@ template <bool NT>
 struct OpMid;
 template <bool NT>
 struct op_unroll<OpMid<NT>> {
-    static constexpr int value = LBK_MID_UNROLL;
+    static constexpr int value = 8;
 };
 
 template <int K, class Op>
 __device__ __forceinline__ void stream(const Op& op, const Seg& s, const Geo& geo, double (&acc)[K], int u0 = 0) {
-    if (LBK_PIPELINE && s.len == geo.L && u0 == 0) {
-        stream_pipelined(op, s, acc);
-        return;
-    }
     if (s.len == geo.L) {
         constexpr int U = op_unroll<Op>::value;
         if constexpr (U > 4)
@@ -905,14 +857,10 @@ __device__ __forceinline__ void stream_stencil(const Op& op, const Seg& s, doubl
     }
 }
 
-#ifndef LBK_LDS_HALO
-#define LBK_LDS_HALO 1
-#endif
-
 // stencil ops over full segments exchange row halos through LDS; everything else streams
 template <int K, class Op>
 __device__ __forceinline__ void stream_halo(const Op& op, const Seg& s, const Geo& geo, double (&acc)[K]) {
-    if constexpr (LBK_LDS_HALO && Op::kStencil) {
+    if constexpr (Op::kStencil) {
         if (s.len == geo.L) {
             stream_stencil(op, s, acc);
             return;
@@ -929,22 +877,13 @@ __device__ __forceinline__ void st2(double* p, double2 v, bool v0, bool v1) {
         st2m(p, v, v0, v1);
 }
 
-// acc = fma(a, b, acc) for the valid elements of a lane pair
-template <bool MASK, bool NT>
+// a work vector (q / r / d): always temporal, see ldw
+template <bool MASK>
 __device__ __forceinline__ void st2w(double* p, double2 v, bool v0, bool v1) {
-    st2<MASK, NT && !LBK_WST_T>(p, v, v0, v1);
+    st2<MASK, false>(p, v, v0, v1);
 }
 
-template <bool MASK, bool NT>
-__device__ __forceinline__ void st2x(double* p, double2 v, bool v0, bool v1) {
-    st2<MASK, NT && !LBK_XG_T>(p, v, v0, v1);
-}
-// level 3: the new history pair (s, y: the next two-loop's first reads)
-template <bool MASK, bool NT>
-__device__ __forceinline__ void st2h(double* p, double2 v, bool v0, bool v1) {
-    st2<MASK, NT && !LBK_SY_T>(p, v, v0, v1);
-}
-
+// acc = fma(a, b, acc) for the valid elements of a lane pair
 template <bool MASK>
 __device__ __forceinline__ double fma2(double2 a, double2 b, double acc, bool v0, bool v1) {
     if (!MASK || v0) acc = fma(a.x, b.x, acc);
@@ -984,7 +923,7 @@ struct OpAxpyDot {  // q = qin - alpha y;  acc += s . q       (lbfgs.cpp:133-137
         double2 q, y, s;
     };
     __device__ void load(Row& r, int64_t i) const {
-        r.q = ldw<NT>(qin + i);
+        r.q = ldw(qin + i);
         r.y = ldv<NT>(y + i);
         r.s = ldv<NT>(s + i);
     }
@@ -993,7 +932,7 @@ struct OpAxpyDot {  // q = qin - alpha y;  acc += s . q       (lbfgs.cpp:133-137
         double2 qn;
         qn.x = r.q.x - alpha * r.y.x;
         qn.y = r.q.y - alpha * r.y.y;
-        st2w<MASK, NT>(qout + i, qn, v0, v1);
+        st2w<MASK>(qout + i, qn, v0, v1);
         acc[0] = fma2<MASK>(r.s, qn, acc[0], v0, v1);
     }
 };
@@ -1024,7 +963,7 @@ struct OpMid {  // r = (qin - alpha0 y0) * gamma;  acc += y0 . r      (:134-137,
         double2 q, y;
     };
     __device__ void load(Row& r, int64_t i) const {
-        r.q = ldw<NT>(qin + i);
+        r.q = ldw(qin + i);
         r.y = ldv<NT>(y0 + i);
     }
     template <bool MASK>
@@ -1032,7 +971,7 @@ struct OpMid {  // r = (qin - alpha0 y0) * gamma;  acc += y0 . r      (:134-137,
         double2 rr;
         rr.x = (r.q.x - alpha * r.y.x) * gamma;
         rr.y = (r.q.y - alpha * r.y.y) * gamma;
-        st2w<MASK, NT>(rout + i, rr, v0, v1);
+        st2w<MASK>(rout + i, rr, v0, v1);
         publish_edges(edge_slot, i, n_loc, g_lo, g_hi, rr, v0, v1);
         acc[0] = fma2<MASK>(r.y, rr, acc[0], v0, v1);
     }
@@ -1053,7 +992,7 @@ struct OpAxpy2Dot {  // r += s (alpha - beta);  acc += ynext . r      (:159-164)
         double2 r, s, y;
     };
     __device__ void load(Row& w, int64_t i) const {
-        w.r = ldw<NT>(rin + i);
+        w.r = ldw(rin + i);
         w.s = ldv<NT>(s + i);
         w.y = ldv<NT>(yn + i);
     }
@@ -1062,7 +1001,7 @@ struct OpAxpy2Dot {  // r += s (alpha - beta);  acc += ynext . r      (:159-164)
         double2 rn;
         rn.x = w.r.x + w.s.x * coef;
         rn.y = w.r.y + w.s.y * coef;
-        st2w<MASK, NT>(r + i, rn, v0, v1);
+        st2w<MASK>(r + i, rn, v0, v1);
         publish_edges(edge_slot, i, n_loc, g_lo, g_hi, rn, v0, v1);
         acc[0] = fma2<MASK>(w.y, rn, acc[0], v0, v1);
     }
@@ -1082,16 +1021,16 @@ struct OpLast {  // d = -(r + s (alpha - beta));  acc += g . d        (:163-171)
         double2 r, s, g;
     };
     __device__ void load(Row& w, int64_t i) const {
-        w.r = ldw<NT>(r + i);
+        w.r = ldw(r + i);
         w.s = ldv<NT>(s + i);
-        w.g = ldx<NT>(g + i);
+        w.g = ldv<NT>(g + i);
     }
     template <bool MASK>
     __device__ void apply(Row& w, int64_t i, int64_t, bool v0, bool v1, double (&acc)[1]) const {
         double2 d;
         d.x = -(w.r.x + w.s.x * coef);
         d.y = -(w.r.y + w.s.y * coef);
-        st2w<MASK, NT>(dout + i, d, v0, v1);
+        st2w<MASK>(dout + i, d, v0, v1);
         publish_edges(edge_slot, i, n_loc, g_lo, g_hi, d, v0, v1);
         acc[0] = fma2<MASK>(w.g, d, acc[0], v0, v1);
     }
@@ -1113,7 +1052,7 @@ struct OpNegDot {  // d = -g;  acc += g . d                          (:90, :151-
         double2 d;
         d.x = -w.g.x;
         d.y = -w.g.y;
-        st2w<MASK, NT>(dout + i, d, v0, v1);
+        st2w<MASK>(dout + i, d, v0, v1);
         publish_edges(edge_slot, i, n_loc, g_lo, g_hi, d, v0, v1);
         acc[0] = fma2<MASK>(w.g, d, acc[0], v0, v1);
     }
@@ -1152,10 +1091,8 @@ __device__ __forceinline__ void run_pass(const Op& op, const Geo& geo, const Red
 // values, so a full segment issues its first row group's loads before it polls; the wait for the
 // xGMI hop runs under those loads instead of ahead of them. coef() is called by every thread (it
 // synchronises the workgroup). The rows are applied and accumulated in the same order as
-// run_pass, so the bits are the same.
-#ifndef LBK_FOLD_PREFETCH
-#define LBK_FOLD_PREFETCH 1  // A/B: 0 polls before any load, as round 3's first folded consumers
-#endif
+// run_pass, so the bits are the same. (Polling before any load, as round 3's first folded
+// consumers did, was measured and removed.)
 template <class Op, int K, class Coef>
 __device__ __forceinline__ void run_pass_prefetch(Op op, const Geo& geo, const Red& red, Coef coef) {
     const Seg s = seg_setup(geo);
@@ -1163,7 +1100,7 @@ __device__ __forceinline__ void run_pass_prefetch(Op op, const Geo& geo, const R
 #pragma unroll
     for (int k = 0; k < K; ++k) acc[k] = 0.0;
     constexpr int U = op_unroll<Op>::value;
-    if (LBK_FOLD_PREFETCH && s.len == geo.L && s.nrows >= U) {
+    if (s.len == geo.L && s.nrows >= U) {
         typename Op::Row r[U];
         load_group<U, K>(op, s, 0, r);
         op.set_coef(coef());
@@ -1291,25 +1228,18 @@ struct DirArgs {
     unsigned long long tmo;
 };
 
-// A/B: LBK_DIR_NT=1 streams the direction source (d, or r of the last second-loop pass) of the
-// commit and the trials non-temporal
-#ifndef LBK_DIR_NT
-#define LBK_DIR_NT 0
-#endif
-template <bool NT>
-__device__ __forceinline__ double2 ldd(const double* p) {
-    return LBK_DIR_NT ? ldv<NT>(p) : ldw<NT>(p);
-}
+// The direction source (d, or r of the last second-loop pass) is a work vector: the commit and the
+// trials read it temporal (streaming it non-temporal was measured and removed).
 template <int DMODE, bool NT>
 __device__ __forceinline__ double2 load_dir(const DirArgs& da, int64_t i, double2 gv) {
     double2 d;
     if (DMODE == LBK_D_BUF) {
-        d = ldd<NT>(da.dsrc + i);
+        d = ldw(da.dsrc + i);
     } else if (DMODE == LBK_D_NEG_G) {
         d.x = -gv.x;
         d.y = -gv.y;
     } else {
-        const double2 rv = ldd<NT>(da.dsrc + i);
+        const double2 rv = ldw(da.dsrc + i);
         const double2 sv = ldv<NT>(da.s + i);
         d.x = -(rv.x + sv.x * da.coef);
         d.y = -(rv.y + sv.y * da.coef);
@@ -1335,6 +1265,25 @@ __device__ __forceinline__ bool needs_halo() {
     return OBJ == LBK_OBJ_ROSENBROCK || OBJ == LBK_OBJ_QUAD_TRIDIAG;
 }
 
+// d at the halo element hi (-1 <= hi <= n_loc) of the row at local index i, per DMODE: the
+// neighbour rank's ghost (sharded), another segment's flagged edge word (cooperative iteration),
+// or the vectors themselves
+template <int DMODE>
+__device__ __forceinline__ double halo_dir(const DirArgs& da, int64_t i, int64_t hi, int64_t n_loc) {
+    if (DMODE == LBK_D_BUF && da.ghost && (hi == -1 || hi == n_loc)) return ghost_d(da, hi, n_loc);
+    if (DMODE == LBK_D_TWOLOOP && da.ghost && (hi == -1 || hi == n_loc))
+        return -(ghost_d(da, hi, n_loc) + da.s[hi] * da.coef);  // neighbour's edge r, s ghost
+    if (DMODE == LBK_D_TWOLOOP && da.redge && hi >= 0 && hi < n_loc && hi / da.L != i / da.L) {
+        // r of another workgroup's segment, written in this launch: its published edge
+        // (write-through), not the plain-stored vector
+        const int64_t sg = hi / da.L;
+        const double rv = ll_load(da.redge + ((hi == sg * da.L ? 1 : 2) * LBK_LL_SEGS + sg) * 2, da.redge_seq,
+                                  da.err, da.tmo);
+        return -(rv + da.s[hi] * da.coef);
+    }
+    return load_dir1<DMODE>(da, hi);
+}
+
 // halo value z = x + alpha d at local index i-1 (lane 0) or i+2 (lane 63)
 template <int OBJ, bool NO_DIR, int DMODE>
 __device__ __forceinline__ double halo_z(const double* __restrict__ x, const DirArgs& da, double alpha,
@@ -1348,21 +1297,7 @@ __device__ __forceinline__ double halo_z(const double* __restrict__ x, const Dir
                 if (NO_DIR) {
                     zh = x[hi];
                 } else {
-                    double dh;
-                    if (DMODE == LBK_D_BUF && da.ghost && (hi == -1 || hi == n_loc))
-                        dh = ghost_d(da, hi, n_loc);
-                    else if (DMODE == LBK_D_TWOLOOP && da.ghost && (hi == -1 || hi == n_loc))
-                        dh = -(ghost_d(da, hi, n_loc) + da.s[hi] * da.coef);  // neighbour's edge r, s ghost
-                    else if (DMODE == LBK_D_TWOLOOP && da.redge && hi >= 0 && hi < n_loc && hi / da.L != i / da.L) {
-                        // r of another workgroup's segment, written in this launch: its published
-                        // edge (write-through), not the plain-stored vector
-                        const int64_t sg = hi / da.L;
-                        const double rv = ll_load(da.redge + ((hi == sg * da.L ? 1 : 2) * LBK_LL_SEGS + sg) * 2,
-                                                  da.redge_seq, da.err, da.tmo);
-                        dh = -(rv + da.s[hi] * da.coef);
-                    } else
-                        dh = load_dir1<DMODE>(da, hi);
-                    zh = x[hi] + alpha * dh;
+                    zh = x[hi] + alpha * halo_dir<DMODE>(da, i, hi, n_loc);
                 }
             }
         }
@@ -1371,7 +1306,7 @@ __device__ __forceinline__ double halo_z(const double* __restrict__ x, const Dir
 }
 
 // (x, d) at local element hi (-1 <= hi <= n_loc; zeros outside), d per DMODE: halo operands
-template <int DMODE, bool REDGE = false>
+template <int DMODE>
 __device__ __forceinline__ double2 xd_at(const double* __restrict__ x, const DirArgs& da, int64_t hi, int64_t n_loc) {
     if (hi < -1 || hi > n_loc) return make_double2(0.0, 0.0);
     double dh;
@@ -1379,15 +1314,7 @@ __device__ __forceinline__ double2 xd_at(const double* __restrict__ x, const Dir
         dh = ghost_d(da, hi, n_loc);
     else if (DMODE == LBK_D_TWOLOOP && da.ghost && (hi == -1 || hi == n_loc))
         dh = -(ghost_d(da, hi, n_loc) + da.s[hi] * da.coef);
-    else if (REDGE && DMODE == LBK_D_TWOLOOP && da.redge && hi >= 0 && hi < n_loc &&
-             (hi == (hi / da.L) * da.L || hi == (hi / da.L) * da.L + da.L - 1)) {
-        // persistent iteration (stencil walk): a segment edge's r, written in this launch by the
-        // workgroup that owns that segment - its published edge word (as halo_z)
-        const int64_t sg = hi / da.L;
-        const double rv = ll_load(da.redge + ((hi == sg * da.L ? 1 : 2) * LBK_LL_SEGS + sg) * 2, da.redge_seq,
-                                  da.err, da.tmo);
-        dh = -(rv + da.s[hi] * da.coef);
-    } else
+    else
         dh = load_dir1<DMODE>(da, hi);
     return make_double2(x[hi], dh);
 }
@@ -1402,22 +1329,7 @@ __device__ __forceinline__ double2 halo_xd(const double* __restrict__ x, const D
         const int lane = threadIdx.x & 63;
         if (lane == 0 || lane == 63) {
             const int64_t hi = (lane == 0) ? i - 1 : i + 2;
-            if (hi >= -1 && hi <= n_loc) {
-                double dh;
-                if (DMODE == LBK_D_BUF && da.ghost && (hi == -1 || hi == n_loc))
-                    dh = ghost_d(da, hi, n_loc);
-                else if (DMODE == LBK_D_TWOLOOP && da.ghost && (hi == -1 || hi == n_loc))
-                    dh = -(ghost_d(da, hi, n_loc) + da.s[hi] * da.coef);
-                else if (DMODE == LBK_D_TWOLOOP && da.redge && hi >= 0 && hi < n_loc && hi / da.L != i / da.L) {
-                    // cooperative iteration: another workgroup's r from this launch (as halo_z)
-                    const int64_t sg = hi / da.L;
-                    const double rv = ll_load(da.redge + ((hi == sg * da.L ? 1 : 2) * LBK_LL_SEGS + sg) * 2,
-                                              da.redge_seq, da.err, da.tmo);
-                    dh = -(rv + da.s[hi] * da.coef);
-                } else
-                    dh = load_dir1<DMODE>(da, hi);
-                xd = make_double2(x[hi], dh);
-            }
+            if (hi >= -1 && hi <= n_loc) xd = make_double2(x[hi], halo_dir<DMODE>(da, i, hi, n_loc));
         }
     }
     return xd;
@@ -1466,11 +1378,11 @@ struct OpObjective {
         double zh;
     };
     __device__ void load(Row& r, int64_t i) const {
-        const double2 xv = ldx<NT>(x + i);
+        const double2 xv = ldv<NT>(x + i);
         if (NO_DIR) {
             r.z = xv;
         } else {
-            r.d = ldw<NT>(da.dsrc + i);
+            r.d = ldw(da.dsrc + i);
             r.z.x = xv.x + alpha * r.d.x;
             r.z.y = xv.y + alpha * r.d.y;
         }
@@ -1480,7 +1392,7 @@ struct OpObjective {
     __device__ void apply(Row& r, int64_t i, int64_t e0, bool v0, bool v1, double (&acc)[2]) const {
         const double2 g = objective_pair<OBJ, MASK>(r.z, r.zh, e0, n, v0, v1, acc[0], WITH_G);
         if (WITH_G) {
-            if (gout) st2x<MASK, NT>(gout + i, g, v0, v1);
+            if (gout) st2<MASK, NT>(gout + i, g, v0, v1);
             acc[1] = NO_DIR ? fma2<MASK>(g, g, acc[1], v0, v1) : fma2<MASK>(g, r.d, acc[1], v0, v1);
         }
     }
@@ -1498,9 +1410,7 @@ __global__ __launch_bounds__(LB_BLOCK) void k_objective(const double* __restrict
 //   [GD] g.d  [F] f  [SY] s.y  [YY] y.y  [GG] g_new.g_new  [SG] s.g_new  [DPHI] g_new.d
 // CAND: also f(x + cand d) at the line search's next backtracking step [FC] (no extra bytes:
 // x and d are in registers), so a rejected first step needs no trial pass for the second.
-// REDGE: the persistent iteration's commit (k_persist_iter), whose stencil halos at segment edges
-// come from the published edge words
-template <int OBJ, int DMODE, bool NT, bool CAND = false, bool REDGE = false>
+template <int OBJ, int DMODE, bool NT, bool CAND = false>
 struct OpCommit {
     static constexpr int K = CAND ? 8 : 7;
     const double* __restrict__ x;
@@ -1518,14 +1428,14 @@ struct OpCommit {
     };
     static constexpr bool kStencil = OBJ != LBK_OBJ_NONE && (OBJ == LBK_OBJ_ROSENBROCK || OBJ == LBK_OBJ_QUAD_TRIDIAG);
     __device__ void load_core(Row& r, int64_t i) const {
-        r.x = ldx<NT>(x + i);
-        r.g = ldx<NT>(da.g + i);
+        r.x = ldv<NT>(x + i);
+        r.g = ldv<NT>(da.g + i);
         r.d = load_dir<DMODE, NT>(da, i, r.g);
         if (OBJ == LBK_OBJ_NONE) r.gx = ldv<NT>(gn + i);
         r.z.x = r.x.x + alpha * r.d.x;
         r.z.y = r.x.y + alpha * r.d.y;
     }
-    __device__ double2 halo_mem(int64_t hi) const { return xd_at<DMODE, REDGE>(x, da, hi, n_loc); }
+    __device__ double2 halo_mem(int64_t hi) const { return xd_at<DMODE>(x, da, hi, n_loc); }
     __device__ double2 edge_first(const Row& r) const { return make_double2(r.x.x, r.d.x); }
     __device__ double2 edge_last(const Row& r) const { return make_double2(r.x.y, r.d.y); }
     __device__ void set_halo(Row& r, double2 xd) const {
@@ -1533,8 +1443,8 @@ struct OpCommit {
         if (CAND) r.zch = xd.x + cand * xd.y;
     }
     __device__ void load(Row& r, int64_t i) const {
-        r.x = ldx<NT>(x + i);
-        r.g = ldx<NT>(da.g + i);
+        r.x = ldv<NT>(x + i);
+        r.g = ldv<NT>(da.g + i);
         r.d = load_dir<DMODE, NT>(da, i, r.g);
         if (OBJ == LBK_OBJ_NONE) r.gx = ldv<NT>(gn + i);
         r.z.x = r.x.x + alpha * r.d.x;
@@ -1560,16 +1470,16 @@ struct OpCommit {
             g2 = r.gx;
         } else {
             g2 = objective_pair<OBJ, MASK>(r.z, r.zh, e0, n, v0, v1, acc[LBK_C_F], true);
-            st2x<MASK, NT>(gn + i, g2, v0, v1);
+            st2<MASK, NT>(gn + i, g2, v0, v1);
         }
-        st2x<MASK, NT>(xn + i, r.z, v0, v1);
+        st2<MASK, NT>(xn + i, r.z, v0, v1);
         double2 sv, yv;
         sv.x = r.z.x - r.x.x;
         sv.y = r.z.y - r.x.y;
         yv.x = g2.x - r.g.x;
         yv.y = g2.y - r.g.y;
-        st2h<MASK, NT>(so + i, sv, v0, v1);
-        st2h<MASK, NT>(yo + i, yv, v0, v1);
+        st2<MASK, NT>(so + i, sv, v0, v1);
+        st2<MASK, NT>(yo + i, yv, v0, v1);
         acc[LBK_C_GD] = fma2<MASK>(r.g, r.d, acc[LBK_C_GD], v0, v1);
         acc[LBK_C_SY] = fma2<MASK>(sv, yv, acc[LBK_C_SY], v0, v1);
         acc[LBK_C_YY] = fma2<MASK>(yv, yv, acc[LBK_C_YY], v0, v1);
@@ -1579,16 +1489,10 @@ struct OpCommit {
     }
 };
 
-#ifndef LBK_COMMIT_WAVES
-#define LBK_COMMIT_WAVES 0  // A/B: > 0 asks the register allocation for that many waves per SIMD
-#endif
-#if LBK_COMMIT_WAVES > 0
-#define LBK_COMMIT_ATTR __attribute__((amdgpu_waves_per_eu(LBK_COMMIT_WAVES)))
-#else
-#define LBK_COMMIT_ATTR
-#endif
+// No waves-per-SIMD attribute: asking the register allocation for 4 waves spills 82 VGPRs (DESIGN.md,
+// round-6 table item 2); the compile-time switch for it was removed.
 template <int OBJ, int DMODE, bool NT, bool CAND = false>
-__global__ __launch_bounds__(LB_BLOCK) LBK_COMMIT_ATTR void k_commit(const double* __restrict__ x, DirArgs da, double alpha,
+__global__ __launch_bounds__(LB_BLOCK) void k_commit(const double* __restrict__ x, DirArgs da, double alpha,
                                                      double* __restrict__ xn, double* __restrict__ gn,
                                                      double* __restrict__ so, double* __restrict__ yo,
                                                      Geo geo, Red red, double cand = 0.0) {
@@ -1639,9 +1543,9 @@ struct OpTrials {
     };
     static constexpr bool kStencil = OBJ == LBK_OBJ_ROSENBROCK || OBJ == LBK_OBJ_QUAD_TRIDIAG;
     __device__ void load_core(Row& r, int64_t i) const {
-        r.x = ldx<NT>(x + i);
+        r.x = ldv<NT>(x + i);
         double2 gv = make_double2(0.0, 0.0);
-        if (DMODE == LBK_D_NEG_G) gv = ldx<NT>(da.g + i);
+        if (DMODE == LBK_D_NEG_G) gv = ldv<NT>(da.g + i);
         r.d = load_dir<DMODE, NT>(da, i, gv);
     }
     __device__ double2 halo_mem(int64_t hi) const { return xd_at<DMODE>(x, da, hi, n_loc); }
@@ -1785,8 +1689,8 @@ struct OpVfCommit {
     };
     // x, g, the basis and z = x + alpha d (and x + ac[j] d) of local elements i, i+1
     __device__ void load(Row& r, int64_t i) const {
-        r.x = ldx<NT>(x + i);
-        r.g = ldx<NT>(g + i);
+        r.x = ldv<NT>(x + i);
+        r.g = ldv<NT>(g + i);
 #pragma unroll
         for (int l = 0; l < 2 * HB; ++l)
             if (l < 2 * B.h) r.b[l] = ldv<NT>(B.b[l] + i);
@@ -1868,15 +1772,15 @@ struct OpVfCommit {
     template <bool MASK>
     __device__ void apply(Row& r, int64_t i, int64_t e0, bool v0, bool v1, double (&acc)[K]) const {
         const double2 g2 = objective_pair<OBJ, MASK>(r.z, r.zh, e0, n, v0, v1, acc[LBK_VF_F], true);
-        st2x<MASK, NT>(gn + i, g2, v0, v1);
-        st2x<MASK, NT>(xn + i, r.z, v0, v1);
+        st2<MASK, NT>(gn + i, g2, v0, v1);
+        st2<MASK, NT>(xn + i, r.z, v0, v1);
         double2 sv, yv;
         sv.x = r.z.x - r.x.x;
         sv.y = r.z.y - r.x.y;
         yv.x = g2.x - r.g.x;
         yv.y = g2.y - r.g.y;
-        st2h<MASK, NT>(so + i, sv, v0, v1);
-        st2h<MASK, NT>(yo + i, yv, v0, v1);
+        st2<MASK, NT>(so + i, sv, v0, v1);
+        st2<MASK, NT>(yo + i, yv, v0, v1);
         acc[LBK_VF_SY] = fma2<MASK>(sv, yv, acc[LBK_VF_SY], v0, v1);
         acc[LBK_VF_YY] = fma2<MASK>(yv, yv, acc[LBK_VF_YY], v0, v1);
         acc[LBK_VF_GG] = fma2<MASK>(g2, g2, acc[LBK_VF_GG], v0, v1);
@@ -2044,7 +1948,7 @@ __global__ void k_vf_ghosts(const double* __restrict__ slot, double* x, double* 
 
 // ---------------------------------------------------------------------------------------
 // Arguments of the one-launch iterations (the cooperative iteration k_coop_iter, the device line
-// search k_coop_search and the persistent forms): the two-loop recursion and the fused first-trial
+// search k_coop_search and the persistent two-loop): the two-loop recursion and the fused first-trial
 // commit of one iteration in ONE launch. (A single-workgroup form for the smallest n measured 1.8x
 // slower at n = 1e4 than the launch sequence, profiles/r01/small_persistent.txt, and was removed.)
 // ---------------------------------------------------------------------------------------
@@ -2083,12 +1987,11 @@ struct SmallArgs {
     unsigned long long* vd;             // device verdict word of this launch ((epoch << 1) | went)
     const unsigned long long* chain;    // the previous speculative launch's verdict word, or nullptr
     unsigned long long chain_want;
-    // persistent forms (k_persist_iter, k_persist_twoloop) only: segments per workgroup (chunks;
-    // 0: strided ownership), alternate the walk direction by pass, the canonical stage 2's
-    // partials and per-group arrival counters (segments, monotonic over passes), the group values
-    // as flagged words [pass parity][component][group][2]
+    // persistent two-loop (k_persist_twoloop) only: segments per workgroup (> 0: workgroup b owns
+    // the chunk [b * spw, (b + 1) * spw)), the canonical stage 2's partials and per-group arrival
+    // counters (segments, monotonic over passes), the group values as flagged words
+    // [pass parity][component][group][2]
     int64_t spw;
-    int alt;
     double* partials;
     unsigned long long* pcnt;
     unsigned long long* gflag;
@@ -2637,104 +2540,56 @@ __device__ __forceinline__ void search_loop(lbk_search& s, Trial&& trial) {
 }
 
 // ---------------------------------------------------------------------------------------
-// Persistent forms for large n (LBFGS_PERSIST=1: the whole iteration, k_persist_iter;
-// LBFGS_PERSIST=2: the two-loop, k_persist_twoloop; VERDICT r02 item 8, the north star's
-// "persistent-block fused two-loop" at configs[2]'s size): one resident grid of G workgroups
-// instead of one workgroup per segment. Workgroup b owns a contiguous chunk of spw canonical
-// segments of every vector (LBFGS_PERSIST_OWN=stride: the segments b, b + G, b + 2G, ..., so the
-// live segments form one window as in the launch sequence; measured slower) and walks them in
-// every pass exactly as the pass kernels walk one segment (the same waves the same rows), storing
-// each segment partial write-through; a workgroup only ever reads back rows it wrote itself.
+// Persistent two-loop for large n (LBFGS_PERSIST=2, k_persist_twoloop; VERDICT r02 item 8, the
+// north star's "persistent-block fused two-loop" at configs[2]'s size): one resident grid of G
+// workgroups instead of one workgroup per segment. Workgroup b owns a contiguous chunk of spw
+// canonical segments of every vector and walks them in every pass exactly as the pass kernels walk
+// one segment (the same waves the same rows); a workgroup only ever reads back rows it wrote itself.
 // Passes with odd sequence numbers walk the owned segments last to first, so a workgroup starts
-// on the segment it touched last, still in the Infinity Cache (the LBFGS_REV effect; A/B
-// LBFGS_PERSIST_ALT=0). After its segments, thread g < 8 of the workgroup adds its
-// segment count in group g to the group's agent-scope counter (monotonic: after pass seq it
-// holds seq * segments-in-group); the arrival that completes a group forms its canonical stage-2
-// tree (group_tree, the same bits as k_group_reduce) and publishes the group values as flagged
-// words. Every workgroup then waits for the 8 group words of each component and forms the
-// fixed-order total. The pass boundaries and stage-2 launches of the launch sequence become one
-// counter round trip plus one flagged hop per pass.
+// on the segment it touched last, still in the Infinity Cache (the LBFGS_REV effect). Each wave
+// keeps its segment sums in LDS and the workgroup meets once after all its segments (the waves
+// read back only rows they wrote themselves), then stores the segment partials write-through.
+// Thread g < 8 of the workgroup then adds its segment count in group g to the group's agent-scope
+// counter (monotonic: after pass seq it holds seq * segments-in-group); the arrival that completes
+// a group forms its canonical stage-2 tree (group_tree, the same bits as k_group_reduce) and
+// publishes the group value as a flagged word. Every workgroup then waits for the 8 group words
+// and forms the fixed-order total. The pass boundaries and stage-2 launches of the launch
+// sequence become one counter round trip plus one flagged hop per pass.
+// Measured and removed: the whole iteration, commit included, in one persistent
+// launch; strided ownership (segments b, b + G, ...); the same walk direction in every pass; two
+// workgroup barriers per owned segment instead of one per pass.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t ceil_pos(int64_t x, int64_t y) { return x <= 0 ? 0 : (x + y - 1) / y; }
-// persist_pass: one workgroup barrier per pass instead of two per owned segment (A/B: -DLBK_PERSIST_SEGBAR=1)
-#ifndef LBK_PERSIST_SEGBAR
-#define LBK_PERSIST_SEGBAR 0
-#endif
-constexpr int kPersistSegMax = 64;
+constexpr int kPersistSegMax = 64;  // segments one workgroup may own: the rows of segp (persist_grid refuses more)
 
-template <int K, bool HALO, class Op>
-__device__ __forceinline__ void persist_pass(const Op& op, const Geo& geo, const SmallArgs& a, int pass, double* slot,
-                                             double* hslot, const double* rvec, double (&tot)[K],
-                                             double (&lds)[4][8], double (&gv)[8][8], int (&last)[8]) {
-    static_assert(K + 2 <= LBK_LL_COMPS && K <= 8, "flagged components");
+// one pass over this workgroup's segments and its in-launch stage 2; returns the pass's total
+template <class Op>
+__device__ __forceinline__ double persist_pass(const Op& op, const Geo& geo, const SmallArgs& a, int pass, double* slot,
+                                               double (&lds)[4][8], double (&gv)[8][8], int (&last)[8]) {
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int64_t G = gridDim.x, b = blockIdx.x;
-    // owned segments: chunk [c0, c0 + cnt) (a.spw > 0), or b, b + G, ... (a.spw == 0)
-    const int64_t c0 = a.spw > 0 ? min(geo.nseg, b * a.spw) : 0;
-    const int64_t cnt = a.spw > 0 ? min(geo.nseg, c0 + a.spw) - c0 : (b < geo.nseg ? (geo.nseg - 1 - b) / G + 1 : 0);
+    // owned segments: the chunk [c0, c0 + cnt), cnt <= kPersistSegMax
+    const int64_t c0 = min(geo.nseg, (int64_t)blockIdx.x * a.spw);
+    const int64_t cnt = min(geo.nseg, c0 + a.spw) - c0;
     const unsigned seq = a.seq_base + (unsigned)pass + 1u;
-    const bool down = (seq & 1u) != 0 && a.alt;
-    unsigned long long* P = a.ll + (size_t)(pass & 1) * LBK_LL_COMPS * LBK_LL_SEGS * 2;
-    // a single-component pass without halos or edges: each wave keeps its segment sums in LDS and
-    // the workgroup meets once after all its segments, instead of twice per segment (the waves read
-    // back only rows they wrote themselves); the same partials, the same bits
+    const bool down = (seq & 1u) != 0;
     __shared__ double segp[kPersistSegMax][4];
-    const bool one_bar = !LBK_PERSIST_SEGBAR && K == 1 && !HALO && rvec == nullptr && cnt <= kPersistSegMax;
     for (int64_t k = 0; k < cnt; ++k) {
         const int64_t kk = down ? cnt - 1 - k : k;
-        const int64_t sidx = a.spw > 0 ? c0 + kk : b + kk * G;
-        const Seg s = seg_at(geo, sidx, t);
-        double acc[K];
-#pragma unroll
-        for (int k2 = 0; k2 < K; ++k2) acc[k2] = 0.0;
-        if constexpr (HALO)
-            stream_halo(op, s, geo, acc);
-        else
-            stream(op, s, geo, acc);
-        if (one_bar) {
-            const double v = wave_sum(acc[0]);
-            if (lane == 0) segp[kk][w] = v;
-            continue;
-        }
-#pragma unroll
-        for (int k2 = 0; k2 < K; ++k2) {
-            const double v = wave_sum(acc[k2]);
-            if (lane == 0) lds[w][k2] = v;
-        }
-        // this segment's vector stores are read by other waves of the workgroup (its edge r below,
-        // the next pass)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __syncthreads();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        if (t == 0) {
-#pragma unroll
-            for (int k2 = 0; k2 < K; ++k2)
-                __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.partials + (int64_t)k2 * LBK_SEGS + sidx),
-                                   dbits((lds[0][k2] + lds[1][k2]) + (lds[2][k2] + lds[3][k2])), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            if (rvec) {  // the segment's first / last r for the commit's halo across segments
-                ll_store(P + ((int64_t)K * LBK_LL_SEGS + sidx) * 2, rvec[s.lb], seq);
-                ll_store(P + ((int64_t)(K + 1) * LBK_LL_SEGS + sidx) * 2, rvec[s.lb + s.len - 1], seq);
-            }
-        }
-        __syncthreads();  // lds reuse
+        const Seg s = seg_at(geo, c0 + kk, t);
+        double acc[1] = {0.0};
+        stream(op, s, geo, acc);
+        const double v = wave_sum(acc[0]);
+        if (lane == 0) segp[kk][w] = v;
     }
-    if (one_bar) {
-        __syncthreads();
-        if (t < cnt) {  // (cnt <= 64: wave 0)
-            const int64_t sidx = a.spw > 0 ? c0 + t : b + (int64_t)t * G;
-            __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.partials + sidx),
-                               dbits((segp[t][0] + segp[t][1]) + (segp[t][2] + segp[t][3])), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    __syncthreads();
+    if (t < cnt)  // (cnt <= 64: wave 0)
+        __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.partials + c0 + t),
+                           dbits((segp[t][0] + segp[t][1]) + (segp[t][2] + segp[t][3])), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
     // wave 0 stored the partials: drained before its counter adds
     if (t < 64) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (t < LBK_GROUPS) {
         const int64_t glo = (int64_t)t * LBK_SEG_PER_GROUP, ghi = min(geo.nseg, glo + LBK_SEG_PER_GROUP);
-        const int64_t c = ghi <= glo       ? 0
-                          : a.spw > 0      ? max((int64_t)0, min(c0 + cnt, ghi) - max(c0, glo))
-                                           : ceil_pos(ghi - b, G) - ceil_pos(glo - b, G);
+        const int64_t c = ghi <= glo ? 0 : max((int64_t)0, min(c0 + cnt, ghi) - max(c0, glo));
         int fl = 0;
         if (c > 0) {
             const unsigned long long old =
@@ -2746,43 +2601,36 @@ __device__ __forceinline__ void persist_pass(const Op& op, const Geo& geo, const
     __syncthreads();
     for (int g = 0; g < LBK_GROUPS; ++g) {
         if (!last[g]) continue;  // uniform: shared
-        // stage 2 of group g, then its values as flagged words
-        __shared__ double glds[4][K];
+        // stage 2 of group g, then its value as a flagged word
+        __shared__ double glds[4][1];
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         double* sg = slot + g * LBK_KMAX;
-        group_tree<K, true>(a.partials, (int64_t)g * LBK_SEG_PER_GROUP, (int64_t)g * LBK_SEG_PER_GROUP, geo.nseg,
-                            LBK_SEG_PER_GROUP, sg, hslot ? hslot + g * LBK_KMAX : nullptr, glds);
+        group_tree<1, true>(a.partials, (int64_t)g * LBK_SEG_PER_GROUP, (int64_t)g * LBK_SEG_PER_GROUP, geo.nseg,
+                            LBK_SEG_PER_GROUP, sg, nullptr, glds);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        if (t < K) ll_store(a.gflag + ((size_t)((pass & 1) * 8 + t) * 8 + g) * 2, sg[t], seq);
+        if (t == 0) ll_store(a.gflag + ((size_t)(pass & 1) * 64 + g) * 2, sg[0], seq);
     }
     // every workgroup: the group values (groups without segments are the slot's 0.0), then the
     // fixed-order total of slot_total()
     const int ng = (int)((geo.nseg + LBK_SEG_PER_GROUP - 1) / LBK_SEG_PER_GROUP);
-    if (t < K * 8) {
-        const int k2 = t >> 3, gg = t & 7;
-        gv[k2][gg] = gg < ng ? ll_load(a.gflag + ((size_t)((pass & 1) * 8 + k2) * 8 + gg) * 2, seq, a.err, a.timeout)
-                             : 0.0;
-    }
+    if (t < 8) gv[0][t] = t < ng ? ll_load(a.gflag + ((size_t)(pass & 1) * 64 + t) * 2, seq, a.err, a.timeout) : 0.0;
     __syncthreads();
-    if (t < K) {
-        double tt = gv[t][0];
+    if (t == 0) {
+        double tt = gv[0][0];
 #pragma unroll
-        for (int q = 1; q < LBK_GROUPS; ++q) tt = tt + gv[t][q];
+        for (int q = 1; q < LBK_GROUPS; ++q) tt = tt + gv[0][q];
         if (blockIdx.x == 0) {
 #pragma unroll
-            for (int q = 0; q < LBK_GROUPS; ++q) {
-                slot[q * LBK_KMAX + t] = gv[t][q];
-                if (hslot) hslot[q * LBK_KMAX + t] = gv[t][q];
-            }
+            for (int q = 0; q < LBK_GROUPS; ++q) slot[q * LBK_KMAX] = gv[0][q];
         }
-        lds[0][t] = tt;
+        lds[0][0] = tt;
     }
     __syncthreads();
-#pragma unroll
-    for (int k2 = 0; k2 < K; ++k2) tot[k2] = lds[0][k2];
+    const double tot = lds[0][0];
     __syncthreads();  // lds / gv reuse by the next pass
+    return tot;
 }
 
 // the persistent passes stream k_mid's pass in op_unroll's default 4-row groups: the launch form's
@@ -2791,98 +2639,60 @@ template <bool NT>
 struct OpMid4 : OpMid<NT> {};
 
 #define SL(sl) (a.slots + (int64_t)(sl) * LBK_SLOT)
-// The two-loop recursion of k_persist_iter (passes P0, the h - 1 first-loop passes, mid and the
-// h - 1 second-loop passes); EDGES: the r passes also publish the segments' edge r for an
-// in-launch commit. Returns the number of passes run; TA / TB hold the two loops' dots.
-template <bool NT, bool EDGES>
-__device__ __forceinline__ int persist_twoloop(const SmallArgs& a, const Geo& geo, double (&lds)[4][8],
-                                               double (&gv)[8][8], double* TA, double* TB, int (&last_flag)[8]) {
+// The two-loop recursion over the persistent passes (P0, the h - 1 first-loop passes, mid and the
+// h - 1 second-loop passes); TA / TB hold the two loops' dots.
+template <bool NT>
+__device__ __forceinline__ void persist_twoloop(const SmallArgs& a, const Geo& geo, double (&lds)[4][8],
+                                                double (&gv)[8][8], double* TA, double* TB, int (&last_flag)[8]) {
     const int h = a.h;
     int pass = 0;
-    double t1[1];
+    double t1;
     const double rho_top = a.rho[h - 1], gamma = a.gamma;
     if (a.p0_from_slot)
-        t1[0] = slot_total(a.p0_slot);
+        t1 = slot_total(a.p0_slot);
     else
-        persist_pass<1, false>(OpDot<NT>{a.S[h - 1], a.g}, geo, a, pass++, SL(a.slot_p0), nullptr, nullptr, t1, lds,
-                               gv, last_flag);
-    if (threadIdx.x == 0) TA[h - 1] = t1[0];
-    double alpha = rho_top * t1[0];
+        t1 = persist_pass(OpDot<NT>{a.S[h - 1], a.g}, geo, a, pass++, SL(a.slot_p0), lds, gv, last_flag);
+    if (threadIdx.x == 0) TA[h - 1] = t1;
+    double alpha = rho_top * t1;
     const double* qsrc = a.g;
     for (int i = h - 2; i >= 0; --i) {  // q = q - alpha_{i+1} y_{i+1};  s_i . q
-        persist_pass<1, false>(OpAxpyDot<NT>{a.q, qsrc, a.Y[i + 1], a.S[i], alpha}, geo, a, pass++, SL(a.slot_a0 + i),
-                               nullptr, nullptr, t1, lds, gv, last_flag);
-        if (threadIdx.x == 0) TA[i] = t1[0];
-        alpha = a.rho[i] * t1[0];
+        t1 = persist_pass(OpAxpyDot<NT>{a.q, qsrc, a.Y[i + 1], a.S[i], alpha}, geo, a, pass++, SL(a.slot_a0 + i), lds,
+                          gv, last_flag);
+        if (threadIdx.x == 0) TA[i] = t1;
+        alpha = a.rho[i] * t1;
         qsrc = a.q;
     }
-    persist_pass<1, false>(OpMid4<NT>{{a.r, qsrc, a.Y[0], alpha, gamma}}, geo, a, pass++, SL(a.slot_b0), nullptr,
-                           EDGES && h == 1 ? a.r : nullptr, t1, lds, gv, last_flag);
-    if (threadIdx.x == 0) TB[0] = t1[0];
+    t1 = persist_pass(OpMid4<NT>{{a.r, qsrc, a.Y[0], alpha, gamma}}, geo, a, pass++, SL(a.slot_b0), lds, gv, last_flag);
+    if (threadIdx.x == 0) TB[0] = t1;
     __syncthreads();
     for (int i = 0; i + 1 < h; ++i) {  // r += s_i (alpha_i - beta_i);  y_{i+1} . r
         const double beta = a.rho[i] * TB[i];
         const double alph = a.rho[i] * TA[i];
-        persist_pass<1, false>(OpAxpy2Dot<NT>{a.r, a.r, a.S[i], a.Y[i + 1], alph - beta}, geo, a, pass++,
-                               SL(a.slot_b0 + i + 1), nullptr, EDGES && i + 2 == h ? a.r : nullptr, t1, lds, gv,
-                               last_flag);
-        if (threadIdx.x == 0) TB[i + 1] = t1[0];
+        t1 = persist_pass(OpAxpy2Dot<NT>{a.r, a.r, a.S[i], a.Y[i + 1], alph - beta}, geo, a, pass++,
+                          SL(a.slot_b0 + i + 1), lds, gv, last_flag);
+        if (threadIdx.x == 0) TB[i + 1] = t1;
         __syncthreads();
     }
-    return pass;
 }
 
-// The whole iteration in one persistent launch (LBFGS_PERSIST=1) lost its A/B at every size
-// (0.95-0.97x the launch sequence at n = 1e8): compiled only into A/B variant
-// builds (-DLBK_PERSIST_ITER=1, tools/build_variant.sh), not into the shipped library.
-#ifndef LBK_PERSIST_ITER
-#define LBK_PERSIST_ITER 0
-#endif
-#if LBK_PERSIST_ITER
-template <int OBJ, bool NT>
-__global__ __launch_bounds__(LB_BLOCK) void k_persist_iter(SmallArgs a, Geo geo) {
-    __shared__ double lds[4][8];
-    __shared__ double gv[8][8];
-    __shared__ double TA[LBK_SMALL_HMAX], TB[LBK_SMALL_HMAX];
-    __shared__ int last_flag[8];
-    const int h = a.h;
-    const double rho_top = a.rho[h - 1], gamma = a.gamma;
-    int pass = persist_twoloop<NT, true>(a, geo, lds, gv, TA, TB, last_flag);
-    const int rp = pass - 1;
-    DirArgs da = {a.r, a.S[h - 1], a.g, 0.0, nullptr, nullptr, rho_top, nullptr, geo.g_lo, geo.g_hi,
-                  a.ll + (size_t)(rp & 1) * LBK_LL_COMPS * LBK_LL_SEGS * 2, geo.L, a.seq_base + (unsigned)rp + 1u, a.err,
-                  a.timeout};
-    {
-        const double beta = rho_top * TB[h - 1];
-        const double alph = rho_top * TA[h - 1];
-        da.coef = alph - beta;
-    }
-    double t8[8];
-    persist_pass<8, true>(OpCommit<OBJ, LBK_D_TWOLOOP, NT, true, true>{a.x, da, a.a0, a.xn, a.gn, a.so, a.yo, geo.n,
-                                                                       geo.n_loc, a.cand},
-                          geo, a, pass++, SL(a.slot_c), HS(a.slot_c), nullptr, t8, lds, gv, last_flag);
-    coop_publish(a, 1, rho_top, gamma);
-}
-#endif  // LBK_PERSIST_ITER
-
-// The persistent two-loop alone (LBFGS_PERSIST=2; the north star's "persistent-block fused
+// The persistent two-loop (LBFGS_PERSIST=2; the north star's "persistent-block fused
 // two-loop"): one resident grid runs all 2h (or 2h - 1) two-loop passes of an iteration, the
 // m-deep s/y ring streamed by the same workgroups pass after pass, with the in-launch stage 2 of
 // persist_pass; the commit follows as its own launch and reads the passes' slots as after the
 // launch sequence. Without the commit's registers (162 VGPRs, 3 waves per SIMD) the grid keeps the
 // two-loop passes' occupancy. Every workgroup reads only the rows it wrote itself in an earlier
 // pass (same segments, same waves), so no vector data crosses workgroups inside the launch.
-#ifndef LBK_PERSIST2_WAVES
-#define LBK_PERSIST2_WAVES 4  // waves per SIMD the register allocation must allow
-#endif
+// (The whole iteration in one persistent launch, commit included, lost its A/B at every size -
+// 0.95-0.97x the launch sequence at n = 1e8, DESIGN.md §4.1 - and was removed.)
+constexpr int kPersist2Waves = 4;  // waves per SIMD the register allocation must allow
 template <bool NT>
-__global__ __launch_bounds__(LB_BLOCK) __attribute__((amdgpu_waves_per_eu(LBK_PERSIST2_WAVES)))
+__global__ __launch_bounds__(LB_BLOCK) __attribute__((amdgpu_waves_per_eu(kPersist2Waves)))
 void k_persist_twoloop(SmallArgs a, Geo geo) {
     __shared__ double lds[4][8];
     __shared__ double gv[8][8];
     __shared__ double TA[LBK_SMALL_HMAX], TB[LBK_SMALL_HMAX];
     __shared__ int last_flag[8];
-    (void)persist_twoloop<NT, false>(a, geo, lds, gv, TA, TB, last_flag);
+    persist_twoloop<NT>(a, geo, lds, gv, TA, TB, last_flag);
 }
 #undef SL
 
@@ -3019,9 +2829,9 @@ struct OpProbeCommit {
         double2 x, g, r, s;
     };
     __device__ void load(Row& w, int64_t i) const {
-        w.x = ldx<NT>(x + i);
-        w.g = ldx<NT>(g + i);
-        w.r = ldd<NT>(r + i);
+        w.x = ldv<NT>(x + i);
+        w.g = ldv<NT>(g + i);
+        w.r = ldw(r + i);
         w.s = ldv<NT>(s + i);
     }
     template <bool MASK>
@@ -3035,10 +2845,10 @@ struct OpProbeCommit {
         sv.y = z.y - w.x.y;
         yv.x = z.x - w.g.x;
         yv.y = z.y - w.g.y;
-        st2x<MASK, NT>(xn + i, z, v0, v1);
-        st2x<MASK, NT>(gn + i, d, v0, v1);
-        st2h<MASK, NT>(so + i, sv, v0, v1);
-        st2h<MASK, NT>(yo + i, yv, v0, v1);
+        st2<MASK, NT>(xn + i, z, v0, v1);
+        st2<MASK, NT>(gn + i, d, v0, v1);
+        st2<MASK, NT>(so + i, sv, v0, v1);
+        st2<MASK, NT>(yo + i, yv, v0, v1);
         acc[0] = fma2<MASK>(w.g, d, acc[0], v0, v1);
     }
 };
@@ -3150,9 +2960,9 @@ struct lbk_ctx {
     int pend_taken;       // the launch in progress consumes it
     // cooperative small-n iteration (k_coop_iter): nseg <= coop_max (0: off)
     int coop_max;
-    // persistent iteration for large n (LBFGS_PERSIST=1, opt-in A/B): resident workgroups, their
-    // segments per pass, stage-2 counters and flagged group values
-    int persist_on, persist_gmax, persist2_gmax, persist_stride, persist_alt, persist_lds;
+    // persistent two-loop for large n (LBFGS_PERSIST=2, opt-in): the switch's value, the resident
+    // grid's cap, the LDS reservation, stage-2 counters and flagged group values
+    int persist_on, persist2_gmax, persist_lds;
     unsigned long long *persist_cnt, *persist_gflag;
     unsigned long long coop_ll_bytes;
     unsigned long long* coop_ll;   // flagged partials (SmallArgs::ll)

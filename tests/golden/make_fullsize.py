@@ -233,8 +233,8 @@ def make_config4_deep(out_path, iters=13):
     """configs[4]'s whole canonical run (ORC_CANON, the oracle's orc_lbfgs at n = 1e9, m = 10,
     backtracking, `iters` iterations: every trace entry, the history filled to h = m = 10 and three
     steps with the ring full). ~265 GB of host memory (30 resident vectors of 8 GB, the terms buffer,
-    x0 and x): more than this container has, so it runs on a GPU box's host (tools/gpu_r06.sh
-    config4deep, OpenMP over the oracle's vector loops) and writes `out_path`; `merge_config4_deep`
+    x0 and x): more than this container has, so it runs on a GPU box's host (OpenMP over
+    the oracle's vector loops) and writes `out_path`; `merge_config4_deep`
     adds it to tests/golden/fullsize/config4_n1e9.json as "canon_deep". Needs no reference build."""
     n, m = 10 ** 9, 10
     t0 = time.time()

@@ -8,8 +8,8 @@ cooperative (<= 256 segments), deferred (<= 1024), reduce kernel (> 1024, 512- a
 segments).
 
 The variants are the shipped forms (DESIGN.md §3 lists each stage-2 form's forward-progress
-assumption and the test here that would catch a violation); LBFGS_PERSIST=1 is compiled out of the
-shipped library (LBK_PERSIST_ITER) and must leave the default path untouched."""
+assumption and the test here that would catch a violation); LBFGS_PERSIST=1 selected a form
+that was removed from the library and must leave the default path untouched."""
 import os
 import sys
 
@@ -25,9 +25,9 @@ pytestmark = pytest.mark.gpu
 # every switch of the shipped library that changes how a one-rank solve runs;
 # the sharded ones (LBFGS_XGMI_FOLD, LBFGS_CU_PARTITION, the time-outs of the exchanges) are
 # covered by tests/test_gpu_xgmi.py and tests/test_gpu_rccl.py, the transfer paths (LBFGS_XFER)
-# by tests/test_gpu_xfer.py. A/B forms measured slower are compiled into variant builds only
-# (tools/build_variant.sh: LBK_PERSIST_ITER, LBK_PERSIST_STRIDE,
-# LBK_PERSIST_ALT, LBK_PERSIST_LDS; the q/r ping-pong was removed).
+# by tests/test_gpu_xfer.py. A/B forms measured slower were removed from the source
+# (the whole iteration in one persistent launch, strided ownership, walks without the alternation,
+# no LDS reservation, the q/r ping-pong).
 KNOBS = ["LBFGS_TICKET", "LBFGS_DEFER", "LBFGS_REV", "LBFGS_NT", "LBFGS_DIRECT", "LBFGS_COOP",
          "LBFGS_PERSIST", "LBFGS_SPEC", "LBFGS_BATCH", "LBFGS_PERSIST_WG", "LBFGS_COLLECT",
          "LBFGS_COLLECT_TIMEOUT", "LBFGS_DEV_SEARCH", "LBFGS_DEV_WOLFE", "LBFGS_SEARCH_TIMEOUT", "LBFGS_WAIT"]
@@ -42,7 +42,7 @@ VARIANTS = {
     "nt1": {"LBFGS_NT": "1"},
     "direct0": {"LBFGS_DIRECT": "0"},
     "coop0": {"LBFGS_COOP": "0"},
-    "persist1_not_shipped": {"LBFGS_PERSIST": "1"},  # compiled out of the library: the default path runs
+    "persist1_not_shipped": {"LBFGS_PERSIST": "1"},  # removed from the library: the default path runs
     "persist2": {"LBFGS_PERSIST": "2"},
     "persist2_wg1": {"LBFGS_PERSIST": "2", "LBFGS_PERSIST_WG": "1"},
     "persist2_nt1": {"LBFGS_PERSIST": "2", "LBFGS_NT": "1"},

@@ -1,7 +1,6 @@
 """The persistent large-n form: LBFGS_PERSIST=2 (k_persist_twoloop, the north
 star's persistent two-loop) runs the two-loop passes in one launch with the commit after it. (The
-whole iteration in one launch, LBFGS_PERSIST=1, lost its A/B at every size and is compiled only into
-variant builds, -DLBK_PERSIST_ITER=1.) One resident grid walks every
+whole iteration in one launch, LBFGS_PERSIST=1, lost its A/B at every size and was removed.) One resident grid walks every
 canonical segment of every pass, with the stage 2 of each pass in the launch. Same per-segment
 arithmetic, same group trees, same fixed-order totals: their trajectories must be the launch
 sequence's bit for bit (and so the canonical oracle's)."""

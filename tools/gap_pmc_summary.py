@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel means of the gap probe's counter passes (tools/gpu_r06.sh gappmc).
+"""Per-kernel means of the gap probe's counter passes.
 
 usage: python tools/gap_pmc_summary.py out.json <pass_dir> [<pass_dir> ...]
 
