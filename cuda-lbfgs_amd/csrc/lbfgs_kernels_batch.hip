@@ -1,7 +1,9 @@
 // lbfgs_kernels_batch.hip — the batched small-n solver (lbfgs_batch_*, include/lbfgs_hip.h): B
 // independent problems that share n, m, objective, line search, constants, tolerance and iteration
 // limit and differ in x0, each solved by ONE workgroup that runs the whole loop of iterate()
-// (lbfgs_driver.c) on the device. A translation unit of its own: twelve large kernels.
+// (lbfgs_driver.c) on the device. A translation unit of its own: twelve large kernels for the stencil
+// objectives (k_batch_solve), and four for dense quadratics with each problem's own A and b
+// (k_batch_solve_dense, further down: the driver's external-objective path restated).
 //
 // Every pass walks the problem's canonical segments one after another with the per-segment code of
 // the launch sequence (seg_at, stream, the Op* operators, wave_sum, ((w0 + w1) + (w2 + w3))), so
@@ -22,6 +24,7 @@
 #define LBK_BATCH_ITERS 64         // iterations per launch (default)
 #define LBK_BATCH_BTW_CAP 4096     // trial passes of one backtracking_wolfe search (see the header)
 #define LBK_BATCH_NVEC(m) (7 + 2 * ((m) + 1))  // x g xn gn d q r, then the m + 1 pairs (s, y)
+#define LBK_BATCH_DENSE_NMAX 4096  // dense quadratics: 128 MiB of A per problem at the limit
 
 namespace {
 
@@ -409,6 +412,384 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) 
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Dense quadratics, every problem with its own A and b (lbfgs_batch_set_dense_quadratics):
+// k_batch_solve_dense restates the external-objective branch of iterate() (lbfgs_driver.c,
+// ext_obj()), not the fused stencil branch above. d is materialised before the search (k_last /
+// k_negdot, whose total is g . d), the search starts with nothing cached, a trial is z = x + alpha d
+// (k_point), the rows of A z (k_dense_rows) and the terms pass (k_terms_dot), the commit reads the
+// gradient it is given (OpCommit<LBK_OBJ_NONE>) and takes f from the evaluation.
+// ---------------------------------------------------------------------------------------
+struct BatchDenseArgs {
+    const double* A;   // [B][n][n], or one [n][n] when astride is 0
+    const double* b;   // [B][n]
+    double* xbase;     // element 0 of problem 0's terms vector t; its trial gradient gt one vector behind
+    int64_t astride;   // n * n, or 0: every problem reads the same matrix
+};
+
+// the host's caches of an external objective (host_point_issue / host_f_at / host_g_at with
+// refcalls = 0): the point in xn, f at the last point, the gradient in gt at the last point
+struct DenseWave {
+    int hz_valid, hf_valid, gt_valid;
+    double hz_alpha, hf_alpha, hf_val, gt_alpha;
+};
+
+struct BatchDenseLds {
+    BatchLds L;
+    DenseWave dw[4];
+};
+
+__device__ __forceinline__ void batch_stage_sync() {  // stores of one stage before loads of the next
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// z = x + alpha d, k_point's arithmetic. k_point also forms the two ghost cells, 0 + alpha * 0; no
+// stage of the dense path reads them, and a step that is not finite would leave NaN there for a
+// later stencil solve on the same batch object, whose halo loads rely on zero ghosts: [0, n) only.
+__device__ __forceinline__ void dense_point(double* z, const double* x, const double* d, double alpha, int64_t n) {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    for (int64_t i = t; i < n; i += LB_BLOCK) z[i] = x[i] + alpha * d[i];
+    batch_stage_sync();
+}
+
+// k_dense_rows inside one workgroup: row i is one wave (wave w: rows w, w + 4, ...; which wave takes
+// which row does not reach the bits), lane l accumulates fma(A_ij, z_j) over j = l, l + 64, ...
+// ascending, then the wave butterfly. The row index is wave-uniform and the loop holds no barrier,
+// so with fewer rows than waves the idle waves fall through to the barrier behind it.
+__device__ __forceinline__ void dense_rows(const double* __restrict__ A, const double* __restrict__ b, const double* z,
+                                           double* g, double* tv, int64_t n) {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    const int lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    for (int64_t i = w; i < n; i += 4) {
+        const double* __restrict__ a = A + i * n;
+        double v = 0.0;
+        for (int64_t j = lane; j < n; j += 64) v = fma(a[j], z[j], v);
+        v = wave_sum(v);
+        if (lane == 0) {
+            const double zi = z[i];
+            g[i] = 2.0 * v + b[i];
+            tv[i] = zi * v + b[i] * zi;
+        }
+    }
+    batch_stage_sync();
+}
+
+template <int LS>
+__global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, BatchDenseArgs dq, Geo geo) {
+    __shared__ BatchDenseLds LD;
+    BatchLds& L = LD.L;
+    const int t = threadIdx.x, m = a.m;
+    const int64_t n = geo.n;
+    BatchWave& W = L.wv[t >> 6];
+    DenseWave& D = LD.dw[t >> 6];
+    BatchState& S = W.st;
+    lbk_search& s = W.s;
+    for (int p = blockIdx.x; p < a.B; p += gridDim.x) {
+        BatchState* G = a.st + p;
+        double* vb = a.base + (int64_t)p * a.pstride;
+        auto vec = [&](int i) { return vb + (int64_t)i * a.vstride; };
+        double* const d = vec(4);
+        double* const q = vec(5);
+        double* const r = vec(6);
+        const double* const Ap = dq.A + (int64_t)p * dq.astride;
+        const double* const bp = dq.b + (int64_t)p * n;
+        double* const tv = dq.xbase + (int64_t)p * 2 * a.vstride;
+        double* const gt = tv + a.vstride;
+        // lbk_dense_eval: the rows at z with the gradient into gout, then f (and gout . gout) from the terms
+        auto eval = [&](const double* z, double* gout, double (&t2)[2]) {
+            dense_rows(Ap, bp, z, gout, tv, n);
+            batch_pass<2>(OpTermsDot<false>{tv, gout}, geo, L, t2);
+            S.vecs += (double)n + 5.0;
+        };
+        if (a.init) {  // a new solve: x = x0, then f, g and g.g at x0
+            S = BatchState();
+            S.status = LBFGS_STATUS_RUNNING;
+            S.h_min = S.h_max = -1;
+            double* x0 = vec(0);
+            for (int64_t i = t; i < n; i += LB_BLOCK) x0[i] = a.xio[(int64_t)p * n + i];
+            batch_stage_sync();
+            double t2[2];
+            eval(x0, vec(1), t2);
+            S.f_cur = t2[0];
+            S.gg = t2[1];
+        } else {
+            if (G->status != LBFGS_STATUS_RUNNING) continue;  // uniform: finished in an earlier launch
+            S = *G;
+        }
+        double* trf = a.trace ? a.tr + (int64_t)p * 3 * a.tr_cap : nullptr;
+        auto trace_push = [&](double f, double gn) {
+            if (!trf) return;
+            if (t == 0 && S.tr_len < a.tr_cap) {
+                trf[S.tr_len] = f;
+                trf[a.tr_cap + S.tr_len] = gn;
+                trf[2 * a.tr_cap + S.tr_len] = __builtin_nan("");
+            }
+            S.tr_len++;
+        };
+
+        for (int it = 0; it < a.iters; ++it) {
+            if (S.k >= a.max_iterations) {
+                trace_push(S.f_cur, sqrt(S.gg));
+                S.status = LBFGS_STATUS_MAX_ITER;
+                break;
+            }
+            const int h = S.h;
+            double* const x = vec(S.flip ? 2 : 0);
+            double* const xn = vec(S.flip ? 0 : 2);
+            double* const g = vec(S.flip ? 3 : 1);
+            double* const gn = vec(S.flip ? 1 : 3);
+            double* const so = vec(7 + 2 * S.free_pair);
+            double* const yo = vec(8 + 2 * S.free_pair);
+            const double gnorm = sqrt(S.gg);
+            trace_push(S.f_cur, gnorm);
+            if (gnorm < a.tol) {
+                S.status = LBFGS_STATUS_CONVERGED;
+                break;
+            }
+            if (S.h_min < 0 || h < S.h_min) S.h_min = h;
+            if (h > S.h_max) S.h_max = h;
+
+            // ---- search direction: the two-loop's passes as in k_batch_solve ----
+            W.dmode = LBK_D_NEG_G;
+            double gamma = 0.0;
+            if (!(S.k == 0 || h == 0)) {
+                int bad_rho = 0;
+                for (int i = h - 1; i >= 0; --i)
+                    if (!isfinite(1.0 / S.sy[S.ring[i]])) bad_rho = 1;
+                if (bad_rho) {
+                    S.ev[2]++;
+                } else {
+                    const int top = S.ring[h - 1];
+                    gamma = S.sy[top] / S.yy[top];
+                    if (gamma <= 0 || !isfinite(gamma))
+                        S.ev[3]++;
+                    else
+                        W.dmode = LBK_D_TWOLOOP;
+                }
+            }
+            if (W.dmode == LBK_D_TWOLOOP) {
+                const int top = S.ring[h - 1];
+                const double rho_top = 1.0 / S.sy[top];
+                double t1[1];
+                if (S.sg_valid) {  // the previous commit's s . g_new
+                    t1[0] = S.sg;
+                } else {
+                    batch_pass<1>(OpDot<false>{vec(7 + 2 * top), g}, geo, L, t1);
+                    S.vecs += 2.0;
+                }
+                W.TA[h - 1] = t1[0];
+                double alpha = rho_top * t1[0];
+                const double* qsrc = g;
+                for (int i = h - 2; i >= 0; --i) {
+                    batch_pass<1>(OpAxpyDot<false>{q, qsrc, vec(8 + 2 * S.ring[i + 1]), vec(7 + 2 * S.ring[i]), alpha},
+                                  geo, L, t1);
+                    S.vecs += 4.0;
+                    W.TA[i] = t1[0];
+                    alpha = (1.0 / S.sy[S.ring[i]]) * t1[0];
+                    qsrc = q;
+                }
+                batch_pass<1>(OpMid<false>{r, qsrc, vec(8 + 2 * S.ring[0]), alpha, gamma}, geo, L, t1);
+                S.vecs += 3.0;
+                for (int i = 0; i + 1 < h; ++i) {
+                    const double rho = 1.0 / S.sy[S.ring[i]];
+                    const double beta = rho * t1[0];
+                    const double alph = rho * W.TA[i];
+                    batch_pass<1>(OpAxpy2Dot<false>{r, r, vec(7 + 2 * S.ring[i]), vec(8 + 2 * S.ring[i + 1]), alph - beta},
+                                  geo, L, t1);
+                    S.vecs += 4.0;
+                }
+                const double beta = rho_top * t1[0];
+                const double alph = rho_top * W.TA[h - 1];
+                W.coef = alph - beta;
+                W.rho_top = rho_top;
+                W.top = top;
+            }
+
+            // ---- d into its buffer (materialize_d: k_last / k_negdot), g . d that pass's total; a
+            // direction that is no descent direction gives way to -g, materialised again (once) ----
+            double gd;
+            for (bool fell_back = false;;) {
+                double t1[1];
+                if (W.dmode == LBK_D_TWOLOOP) {
+                    batch_pass<1>(OpLast<false>{d, r, vec(7 + 2 * W.top), g, W.coef}, geo, L, t1);
+                    S.vecs += 4.0;
+                } else {
+                    batch_pass<1>(OpNegDot<false>{d, g}, geo, L, t1);
+                    S.vecs += 2.0;
+                }
+                gd = t1[0];
+                if (!(gd >= 0) || fell_back) break;
+                S.ev[0]++;
+                W.dmode = LBK_D_NEG_G;
+                fell_back = true;
+            }
+            D.hz_valid = D.hf_valid = D.gt_valid = 0;  // host_invalidate: nothing cached refers to this x, d
+
+            auto point = [&](double alpha) {  // host_point_issue
+                if (D.hz_valid && D.hz_alpha == alpha) return;
+                dense_point(xn, x, d, alpha, n);
+                S.vecs += 3.0;
+                D.hz_valid = 1;
+                D.hz_alpha = alpha;
+                D.hf_valid = 0;
+            };
+            // one evaluation at z(alpha) with the gradient into dst: f is cached with it, and the
+            // gradient when dst is gt (host_g_at's dense branch; host_f_at's is this with dst = gt)
+            auto eval_at = [&](double alpha, double* dst) {
+                point(alpha);
+                double t2[2];
+                eval(xn, dst, t2);
+                D.hf_valid = 1;
+                D.hf_alpha = alpha;
+                D.hf_val = t2[0];
+                if (dst == gt) {
+                    D.gt_valid = 1;
+                    D.gt_alpha = alpha;
+                } else if (D.gt_valid && D.gt_alpha == alpha) {
+                    D.gt_valid = 0;
+                }
+            };
+            auto f_at = [&](double alpha) -> double {  // host_f_at
+                if (!(D.hf_valid && D.hf_alpha == alpha && D.hz_valid && D.hz_alpha == alpha)) eval_at(alpha, gt);
+                return D.hf_val;
+            };
+            auto g_at = [&](double alpha, double* dst) {  // host_g_at
+                if (D.gt_valid && D.gt_alpha == alpha) {
+                    if (dst != gt) {
+                        for (int64_t i = t; i < n; i += LB_BLOCK) dst[i] = gt[i];
+                        batch_stage_sync();
+                        S.vecs += 2.0;
+                    }
+                    return;
+                }
+                eval_at(alpha, dst);
+            };
+
+            // ---- the line search, from the top, nothing cached (no first trial rode a commit) ----
+            __builtin_memset(&s, 0, sizeof s);
+            s.f_x = S.f_cur;
+            s.gd = gd;
+            s.c1 = a.K.c1;
+            s.c2 = a.K.c2;
+            s.amin = a.K.wolfe_interp_min;
+            s.init = a.K.initial_step;
+            s.beta = a.K.backtracking_alpha;
+            s.tol = a.K.backtracking_tol;
+            s.alpha = a.K.initial_step;
+            s.alpha_hi = INFINITY;
+            s.f_lo = s.f_prev = S.f_cur;
+            s.dphi_lo = gd;
+            W.capped = W.passes = 0;
+            // lbfgs_driver.c trial() for an external objective: one step per call, f from its cache or
+            // an evaluation, with need_g the gradient in gt and gt . d; the backtracking-Wolfe search
+            // asks for the gradient before f (line_search.cpp:39-42)
+            auto trial = [&](double alpha, bool need_g, double& f, double& dphi) -> bool {
+                if (LS == 3 && W.passes >= LBK_BATCH_BTW_CAP) {  // the reference's loop has no bound of its own
+                    W.capped = 1;
+                    return false;
+                }
+                W.passes++;
+                const bool g_first = need_g && LS == 3;
+                // (a loop of two steps, not unrolled, so that f_at and g_at are inlined once each)
+#pragma unroll 1
+                for (int step = 0; step < 2; ++step) {
+                    if ((step == 0) == g_first) {
+                        if (need_g) g_at(alpha, gt);
+                    } else {
+                        f = f_at(alpha);
+                    }
+                }
+                if (need_g) {
+                    double t1[1];
+                    batch_pass<1>(OpDot<false>{gt, d}, geo, L, t1);
+                    S.vecs += 2.0;
+                    dphi = t1[0];
+                    S.trials_fg++;
+                } else {
+                    S.trials_f++;
+                }
+                return true;
+            };
+            search_loop<LS>(s, trial);
+            if (W.capped || !s.done) {
+                S.status = LBFGS_ERR_STATE;
+                break;
+            }
+            const double alpha = s.step;
+            if (trf && t == 0 && S.tr_len - 1 < a.tr_cap) trf[2 * a.tr_cap + S.tr_len - 1] = alpha;
+
+            // ---- commit (lbfgs_driver.c commit(), ext_obj): f at the step, then - unless the step
+            // failed - the gradient at the step into gn, and the commit pass that reads it ----
+            const double f_new = f_at(alpha);
+            S.f_cur = f_new;
+            if (alpha < 1e-10) {
+                S.status = LBFGS_STATUS_LS_FAILED;
+                break;
+            }
+            g_at(alpha, gn);
+            {
+                DirArgs db = {};
+                db.dsrc = d;
+                db.g = g;
+                db.g_hi = LBK_GROUPS;
+                batch_pass<7>(OpCommit<LBK_OBJ_NONE, LBK_D_BUF, false, false>{x, db, alpha, xn, gn, so, yo, n, n, 0.0},
+                              geo, L, W.tot);
+            }
+            W.tot[LBK_C_F] = f_new;
+            S.vecs += 7.0;
+            S.commits++;
+            const double sy = W.tot[LBK_C_SY];
+            if (sy > 0) {
+                const int pair = S.free_pair;
+                if (h >= m) {
+                    const int oldest = S.ring[0];
+                    for (int i = 0; i + 1 < m; ++i) S.ring[i] = S.ring[i + 1];
+                    S.ring[m - 1] = pair;
+                    S.free_pair = oldest;
+                } else {
+                    S.ring[h] = pair;
+                    S.h = h + 1;
+                    S.free_pair = h + 1;
+                }
+                S.sy[pair] = sy;
+                S.yy[pair] = W.tot[LBK_C_YY];
+                S.sg_valid = 1;
+                S.sg = W.tot[LBK_C_SG];
+            } else {
+                S.ev[1]++;
+                S.sg_valid = 0;
+            }
+            S.flip ^= 1;
+            S.gg = W.tot[LBK_C_GG];
+            S.k++;
+        }
+
+        if (S.status != LBFGS_STATUS_RUNNING) {  // finished in this launch: x out
+            const double* xc = vec(S.flip ? 2 : 0);
+            for (int64_t i = t; i < n; i += LB_BLOCK) a.xio[(int64_t)p * n + i] = xc[i];
+        }
+        if (t == 0) {
+            *G = S;
+            if (S.status == LBFGS_STATUS_RUNNING) atomicOr(a.running, 1);
+        }
+    }
+}
+
+typedef void (*batch_dense_kernel_t)(BatchArgs, BatchDenseArgs, Geo);
+batch_dense_kernel_t batch_dense_kernel(int ls) {
+    switch (ls) {
+        case 0: return k_batch_solve_dense<0>;
+        case 1: return k_batch_solve_dense<1>;
+        case 2: return k_batch_solve_dense<2>;
+        default: return k_batch_solve_dense<3>;
+    }
+}
+
 typedef void (*batch_kernel_t)(BatchArgs, Geo);
 template <int OBJ>
 batch_kernel_t batch_kernel_ls(int ls) {
@@ -441,6 +822,13 @@ struct lbfgs_batch {
     int* running;
     double* tr;       // device trace, [B][3][tr_cap]
     int tr_cap;
+    // dense quadratics (lbfgs_batch_set_dense_quadratics): the matrices, the linear terms, and per
+    // problem the terms vector t and the trial gradient gt in the vectors' own layout
+    double* dq_A;
+    double* dq_b;
+    double* dq_x;
+    size_t dq_A_doubles;  // capacity of dq_A
+    bool dq_set, dq_shared;
     hipStream_t stream;
     std::vector<BatchState> hst;  // the states after the last solve
     std::vector<double> htr;      // its traces (LBFGS_FLAG_TRACE)
@@ -469,6 +857,15 @@ int lbfgs_batch_plan(int64_t n, int m, int batch, double* bytes) {
     return 0;
 }
 
+int lbfgs_batch_dense_plan(int64_t n, int m, int batch, int shared_A, double* bytes) {
+    double base = 0.0;
+    if (n > LBK_BATCH_DENSE_NMAX || lbfgs_batch_plan(n, m, batch, &base) != 0) return LBFGS_ERR_BAD_ARG;
+    if (bytes)  // the batch, then t and gt and b per problem, then the matrices
+        *bytes = base + (double)batch * 8.0 * (2.0 * (double)batch_vstride(n) + (double)n) +
+                 (shared_A ? 1.0 : (double)batch) * 8.0 * (double)n * (double)n;
+    return 0;
+}
+
 void lbfgs_batch_destroy(lbfgs_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
@@ -478,6 +875,9 @@ void lbfgs_batch_destroy(lbfgs_batch* b) {
     if (b->st) (void)hipFree(b->st);
     if (b->running) (void)hipFree(b->running);
     if (b->tr) (void)hipFree(b->tr);
+    if (b->dq_A) (void)hipFree(b->dq_A);
+    if (b->dq_b) (void)hipFree(b->dq_b);
+    if (b->dq_x) (void)hipFree(b->dq_x);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -538,16 +938,63 @@ int lbfgs_batch_set_launch(lbfgs_batch* b, int max_workgroups, int iters_per_lau
     return 0;
 }
 
+int lbfgs_batch_set_dense_quadratics(lbfgs_batch* b, const double* A, int shared_A, const double* bvec) {
+    if (!b) return LBFGS_ERR_BAD_ARG;
+    b->err[0] = 0;
+    if (!A || !bvec || b->n > LBK_BATCH_DENSE_NMAX) {
+        snprintf(b->err, sizeof b->err, "lbfgs_batch_set_dense_quadratics: A and b, and a batch of n <= %d",
+                 LBK_BATCH_DENSE_NMAX);
+        return LBFGS_ERR_BAD_ARG;
+    }
+    BHIP(b, hipSetDevice(b->device));
+    const size_t nn = (size_t)b->n * (size_t)b->n, B = (size_t)b->B;
+    const size_t a_doubles = shared_A ? nn : nn * B;
+    const size_t xbytes = sizeof(double) * 2 * (size_t)b->vstride * B;
+    b->dq_set = false;
+    bool ok = true;
+    if (!b->dq_b) ok = hipMalloc((void**)&b->dq_b, sizeof(double) * (size_t)b->n * B) == hipSuccess;
+    if (ok && !b->dq_x) {
+        ok = hipMalloc((void**)&b->dq_x, xbytes) == hipSuccess;
+        // ghost cells and padding are zero and stay zero, as the batch's other vectors'
+        if (ok && hipMemsetAsync(b->dq_x, 0, xbytes, b->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(b->dq_x);
+            b->dq_x = nullptr;
+            snprintf(b->err, sizeof b->err, "lbfgs_batch_set_dense_quadratics: hipMemsetAsync failed");
+            return LBFGS_ERR_HIP;
+        }
+    }
+    if (ok && b->dq_A_doubles < a_doubles) {
+        if (b->dq_A) (void)hipFree(b->dq_A);
+        b->dq_A = nullptr;
+        b->dq_A_doubles = 0;
+        ok = hipMalloc((void**)&b->dq_A, sizeof(double) * a_doubles) == hipSuccess;
+        if (ok) b->dq_A_doubles = a_doubles;
+    }
+    if (!ok) {  // the batch stays usable for the stencil objectives
+        (void)hipGetLastError();
+        snprintf(b->err, sizeof b->err, "lbfgs_batch_set_dense_quadratics: out of device memory");
+        return LBFGS_ERR_NOMEM;
+    }
+    BHIP(b, hipMemcpyAsync(b->dq_A, A, sizeof(double) * a_doubles, hipMemcpyHostToDevice, b->stream));
+    BHIP(b, hipMemcpyAsync(b->dq_b, bvec, sizeof(double) * (size_t)b->n * B, hipMemcpyHostToDevice, b->stream));
+    BHIP(b, hipStreamSynchronize(b->stream));
+    b->dq_shared = shared_A != 0;
+    b->dq_set = true;
+    return 0;
+}
+
 int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const lbfgs_constants* k,
                          const double* x0_host, double* x_out_host, int max_iterations, double tolerance,
                          unsigned flags, lbfgs_result* out) {
     if (!b) return LBFGS_ERR_BAD_ARG;
     b->err[0] = 0;
-    if (!x0_host || objective < LBFGS_OBJ_ROSENBROCK || objective > LBFGS_OBJ_QUAD_SEPARABLE ||
+    const bool dense = objective == LBFGS_OBJ_DENSE_QUAD && b->dq_set;
+    if (!x0_host || (!dense && (objective < LBFGS_OBJ_ROSENBROCK || objective > LBFGS_OBJ_QUAD_SEPARABLE)) ||
         line_search < LBFGS_LS_BACKTRACKING || line_search > LBFGS_LS_BACKTRACKING_WOLFE || max_iterations < 0 ||
         (flags & ~(LBFGS_FLAG_TRACE | LBFGS_FLAG_QUIET)) != 0) {
-        snprintf(b->err, sizeof b->err, "lbfgs_batch_minimize: device stencil objectives, the four line searches, "
-                 "LBFGS_FLAG_TRACE / LBFGS_FLAG_QUIET only");
+        snprintf(b->err, sizeof b->err, "lbfgs_batch_minimize: device stencil objectives (the dense quadratic once "
+                 "its data is set), the four line searches, LBFGS_FLAG_TRACE / LBFGS_FLAG_QUIET only");
         return LBFGS_ERR_BAD_ARG;
     }
     const auto t0 = std::chrono::steady_clock::now();
@@ -582,11 +1029,23 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
         a.K = *k;
     else
         lbfgs_constants_default(&a.K);
-    const batch_kernel_t kern = batch_kernel(objective, line_search);
+    const batch_kernel_t kern = dense ? nullptr : batch_kernel(objective, line_search);
+    const batch_dense_kernel_t dkern = dense ? batch_dense_kernel(line_search) : nullptr;
+    BatchDenseArgs dq;
+    memset(&dq, 0, sizeof dq);
+    if (dense) {
+        dq.A = b->dq_A;
+        dq.b = b->dq_b;
+        dq.xbase = b->dq_x + LBK_FRONT;
+        dq.astride = b->dq_shared ? 0 : b->n * b->n;
+    }
     int grid = b->max_wg;
     if (grid <= 0) {  // every workgroup resident: occupancy x CUs
         int per_cu = 0;
-        BHIP(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, LB_BLOCK, 0));
+        if (dense)
+            BHIP(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dkern, LB_BLOCK, 0));
+        else
+            BHIP(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, LB_BLOCK, 0));
         grid = std::max(1, per_cu) * std::max(1, b->cus);
     }
     grid = std::min(grid, b->B);
@@ -599,7 +1058,10 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
     for (;;) {
         int running = 0;
         BHIP(b, hipMemsetAsync(b->running, 0, sizeof(int), b->stream));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(LB_BLOCK), 0, b->stream, a, b->geo);
+        if (dense)
+            hipLaunchKernelGGL(dkern, dim3(grid), dim3(LB_BLOCK), 0, b->stream, a, dq, b->geo);
+        else
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(LB_BLOCK), 0, b->stream, a, b->geo);
         BHIP(b, hipGetLastError());
         BHIP(b, hipMemcpyAsync(&running, b->running, sizeof(int), hipMemcpyDeviceToHost, b->stream));
         BHIP(b, hipStreamSynchronize(b->stream));

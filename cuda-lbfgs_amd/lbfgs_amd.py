@@ -165,6 +165,8 @@ def lib():
     L.lbfgs_batch_trace_len.argtypes = [vp, C.c_int]
     L.lbfgs_batch_trace_get.argtypes = [vp, C.c_int, dp, dp, dp, C.c_int]
     L.lbfgs_batch_events_get.argtypes = [vp, C.c_int, C.POINTER(BatchEvents)]
+    L.lbfgs_batch_dense_plan.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.lbfgs_batch_set_dense_quadratics.argtypes = [vp, vp, C.c_int, vp]
     L.lbfgs_set_device_objective.argtypes = [vp, C.POINTER(DeviceFn)]
     L.lbfgs_minimize_device.argtypes = [vp, C.c_int, C.POINTER(HostFn), C.c_int, C.POINTER(Constants),
                                         vp, vp, C.c_int, C.c_double, C.c_uint, C.POINTER(Result)]
@@ -193,7 +195,7 @@ EXPORTED_SYMBOLS = [
     "lbfgs_spec_stats", "lbfgs_cu_partition", "lbfgs_stream_probe", "lbfgs_stream_probe_variant", "lbfgs_stream_probe_vectors", "lbfgs_vector_address", "lbfgs_coop_info", "lbfgs_wait_stats", "lbfgs_vector_fallbacks", "lbfgs_vector_pool", "lbfgs_search_stats",
     "lbfgs_batch_plan", "lbfgs_batch_create", "lbfgs_batch_destroy", "lbfgs_batch_last_error",
     "lbfgs_batch_set_launch", "lbfgs_batch_minimize", "lbfgs_batch_trace_len", "lbfgs_batch_trace_get",
-    "lbfgs_batch_events_get",
+    "lbfgs_batch_events_get", "lbfgs_batch_dense_plan", "lbfgs_batch_set_dense_quadratics",
     "lbfgs_set_device_objective", "lbfgs_minimize_device", "lbfgs_solver_init_device", "lbfgs_get_x_device",
     "lbfgs_reducer_create", "lbfgs_reducer_destroy", "lbfgs_reducer_dot",
 ]
@@ -301,9 +303,26 @@ def plan(n, m, batch):
     return b.value
 
 
+DENSE_BATCH_NMAX = 4096  # the dense batch's limit on n (lbfgs_batch_dense_plan)
+
+
+def plan_dense(n, m, batch, shared=False):
+    """Device bytes a Batch(n, m, batch) with dense quadratics set would take, the matrices included
+    (one matrix when shared); raises LbfgsError outside the dense batch's limits (lbfgs_batch_dense_plan)."""
+    b = C.c_double()
+    rc = lib().lbfgs_batch_dense_plan(int(n), int(m), int(batch), int(bool(shared)), C.byref(b))
+    if rc != 0:
+        e = LbfgsError(f"lbfgs_batch_dense_plan({n}, {m}, {batch}) failed ({rc}): 1 <= n <= {DENSE_BATCH_NMAX}, "
+                       "1 <= m <= 16, batch >= 1")
+        e.rc = rc
+        raise e
+    return b.value
+
+
 class Batch:
     """`batch` independent small problems (same n, m, objective, line search, constants, tolerance
-    and iteration limit; their own x0) solved at once, one workgroup each, the whole solver loop on
+    and iteration limit; their own x0, and for objective "dense" their own A and b, see
+    set_dense_quadratics) solved at once, one workgroup each, the whole solver loop on
     the device; every problem's result is bit for bit Context.minimize's for it alone.
 
         with L.Batch(n=10_000, m=5, batch=256) as b:
@@ -349,6 +368,24 @@ class Batch:
         rc = lib().lbfgs_batch_set_launch(self.h, int(max_workgroups), int(iters_per_launch))
         if rc != 0:
             self._err("lbfgs_batch_set_launch", rc)
+
+    def set_dense_quadratics(self, A, b):
+        """Data of objective "dense", problem p minimising x'A[p]x + b[p]'x: A of shape (batch, n, n), or
+        (n, n) for one matrix shared by every problem; b of shape (batch, n). float64. Copied to the
+        device; may be called again with new data between solves."""
+        A, b = np.asarray(A), np.asarray(b)
+        if A.dtype != np.float64 or b.dtype != np.float64:
+            raise TypeError(f"set_dense_quadratics: A and b must be float64, got {A.dtype} and {b.dtype}")
+        if A.shape not in ((self.n, self.n), (self.batch, self.n, self.n)):
+            raise ValueError(f"set_dense_quadratics: A has shape {A.shape}, expected ({self.batch}, {self.n}, {self.n}) "
+                             f"or, shared, ({self.n}, {self.n})")
+        if b.shape != (self.batch, self.n):
+            raise ValueError(f"set_dense_quadratics: b has shape {b.shape}, expected ({self.batch}, {self.n})")
+        A, b = np.ascontiguousarray(A), np.ascontiguousarray(b)
+        rc = lib().lbfgs_batch_set_dense_quadratics(self.h, A.ctypes.data_as(C.c_void_p), int(A.ndim == 2),
+                                                    b.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            self._err("lbfgs_batch_set_dense_quadratics", rc)
 
     def minimize(self, objective, X0, line_search="backtracking", max_iterations=1000, tolerance=1e-5,
                  consts=None, trace=False, flags=0, out=None):

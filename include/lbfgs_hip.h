@@ -379,7 +379,8 @@ int lbfgs_trace_enable(lbfgs_ctx* ctx, int on);
 
 /* ---- many small problems at once ------------------------------------------------------- */
 /* A batch solves `batch` independent problems that share n, m, objective, line search, constants,
- * tolerance and iteration limit and differ only in x0, one workgroup per problem, the whole loop of
+ * tolerance and iteration limit and differ in x0 (and, for the dense quadratic, in A and b: see
+ * lbfgs_batch_set_dense_quadratics below), one workgroup per problem, the whole loop of
  * lbfgs_minimize on the device: no host round trip per iteration, hundreds of
  * problems side by side. Each problem's x, f, |g|, iterations, status and trace are bit for bit what
  * lbfgs_minimize gives for that problem alone. Limits: 1 <= n <= 32768, 1 <= m <= 16, the device
@@ -417,6 +418,23 @@ int lbfgs_batch_trace_get(const lbfgs_batch* b, int problem, double* f, double* 
  * "Skipping update", "Invalid rho", "Invalid gamma" (a failed line search is the status) */
 typedef struct { int not_descent, skipped_updates, invalid_rho, invalid_gamma; } lbfgs_batch_events;
 int lbfgs_batch_events_get(const lbfgs_batch* b, int problem, lbfgs_batch_events* out);
+/* Dense quadratics, every problem with its own data: after lbfgs_batch_set_dense_quadratics the
+ * batch also takes LBFGS_OBJ_DENSE_QUAD, problem p minimising f = x'A_p x + b_p'x, still one workgroup
+ * per problem with the whole loop on the device (the rows of A_p z are formed inside the workgroup,
+ * one wave per row), and each result is bit for bit what lbfgs_set_dense_quadratic(A_p, b_p) +
+ * lbfgs_minimize(LBFGS_OBJ_DENSE_QUAD, x0_p) gives, trials_f / trials_fg / commits included. Limits:
+ * 1 <= n <= 4096 (128 MiB of A per problem at the limit), 1 <= m <= 16, the same flags. Without data
+ * set the objective stays LBFGS_ERR_BAD_ARG before anything is launched. Per problem, bytes counts a
+ * dense evaluation as the single-problem path does: n + 5 vectors (the matrix once, x, the terms
+ * twice, the gradient twice). */
+/* no device needed: 0 when (n, m, batch) is within the dense batch's limits, else LBFGS_ERR_BAD_ARG;
+ * *bytes (nullable) = device memory the batch and its matrices would take */
+int lbfgs_batch_dense_plan(int64_t n, int m, int batch, int shared_A, double* bytes);
+/* A: batch x n x n row-major (problem p at p*n*n), or with shared_A = 1 one n x n matrix used by
+ * every problem; b: batch x n. Copies both into the batch object; may be called again with new data.
+ * LBFGS_ERR_BAD_ARG for a batch created with n > 4096; LBFGS_ERR_NOMEM when the device has no room
+ * (the batch object stays usable for the stencil objectives). */
+int lbfgs_batch_set_dense_quadratics(lbfgs_batch* b, const double* A, int shared_A, const double* bvec);
 
 /* ---- canonical reductions on caller-owned device buffers -------------------------------- */
 /* For objectives evaluated on the device (LBFGS_OBJ_DEVICE): the sum of their per-element terms in

@@ -1,0 +1,303 @@
+"""GPU tests of the batched solver on dense quadratics with each problem's own A and b
+(lbfgs_batch_set_dense_quadratics, Batch.set_dense_quadratics): one workgroup per problem, the
+external-objective loop of the driver restated on the device. Every comparison is by bits, never a
+tolerance: the reference is the canonical-order oracle run once per problem on the CPU
+(O.dense_set(A_p, b_p); O.lbfgs("dense", x0_p, ..., mode=O.CANON)) and, for one batch per line
+search, the single-problem path (Context.set_dense_quadratic + Context.minimize), counters included.
+
+Shapes: n = 2 and 3 (fewer rows than waves), 5 (a row beyond a multiple of 4), 10, 100 (a second,
+partial lane stride), 64 / 65 (exactly one lane stride; one element more), 513 (two canonical
+segments, the second of one element), 500 (the largest known-answer fixture); m = 1 (a two-loop with
+no q pass) and m = 5 with more than m + 2 iterations (the ring and the spare pair rotate)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "cuda-lbfgs_amd"))
+import lbfgs_amd as L  # noqa: E402
+import oracle_lib as O  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+SEARCHES = ["backtracking", "interpolation", "wolfe", "backtracking_wolfe"]
+MESSAGES = ["Not a descent direction", "Skipping update", "Invalid rho", "Invalid gamma", "Line search failed"]
+EVENT_KEYS = ["not_descent", "skipped_updates", "invalid_rho", "invalid_gamma"]
+_data = np.load(os.path.join(ROOT, "tests", "golden", "matrices.npz"), allow_pickle=False)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def same_bits(a, b):
+    """Equal bit for bit; a NaN equals a NaN in the same place (its sign and payload are the
+    processor's: x86 and the GPU produce different ones from the same operation)."""
+    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+    na, nb = np.isnan(a), np.isnan(b)
+    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(bits(a[~na]), bits(b[~nb]))
+
+
+def fixture_batch(n, B, period=None):
+    """Problem p of the known-answer data of size n: A_p = mat_n + 0.25 q I, b_p = (1 + q) linear_n,
+    x0 from seed 10 + q in [-2, 2], q = p (or p modulo `period`: the data repeat)."""
+    mat, lin = _data[f"mat{n}"], _data[f"linear{n}"]
+    q = [p if period is None else p % period for p in range(B)]
+    A = np.stack([mat + 0.25 * k * np.eye(n) for k in q])
+    b = np.stack([(1.0 + k) * lin for k in q])
+    X0 = np.stack([O.x0_uniform(n, 10 + k, -2.0, 2.0) for k in q])
+    return A, b, X0
+
+
+def spectrum_batch(n, B, eig, seed):
+    """A_p with the eigenvalues `eig` in a random orthogonal basis, symmetrised; b_p and x0_p random."""
+    A, b, X0 = [], [], []
+    for p in range(B):
+        rs = np.random.RandomState(seed + p)
+        Q, _ = np.linalg.qr(rs.standard_normal((n, n)))
+        M = (Q * eig) @ Q.T
+        A.append((M + M.T) / 2)
+        b.append(rs.uniform(-1.0, 1.0, n))
+        X0.append(O.x0_uniform(n, seed + p, -2.0, 2.0))
+    return np.stack(A), np.stack(b), np.stack(X0)
+
+
+_oracle = {}
+
+
+def oracle(key, A, b, X0, ls, m, maxit, tol, problems=None):
+    """The oracle's runs of the problems of a batch, computed once per key and shared (left unchanged)."""
+    if key not in _oracle:
+        runs = {}
+        for p in (range(len(X0)) if problems is None else problems):
+            O.dense_set(A[p] if A.ndim == 3 else A, b[p])
+            runs[p] = O.lbfgs("dense", X0[p], ls, m, maxit, tol, mode=O.CANON)
+        _oracle[key] = runs
+    return _oracle[key]
+
+
+def message_counts(o):
+    return [sum(1 for line in o["messages"].splitlines() if m in line) for m in MESSAGES]
+
+
+def check_problem(res, p, o, what=""):
+    """x, f, |g|, iterations, status, the f / |g| / alpha traces and the event counts of problem p
+    against its oracle run (after a failed line search the result's f is f at the failed step, which
+    the oracle does not return)."""
+    assert res["status"][p] == o["status"], (what, p, res["status"][p], o["status"])
+    assert res["iterations"][p] == o["iters"], (what, p, res["iterations"][p], o["iters"])
+    assert same_bits(res["x"][p], o["x"]), (what, p)
+    assert same_bits([res["gnorm"][p]], [o["gnorm"][-1]]), (what, p)
+    if o["status"] != "ls_failed":
+        assert same_bits([res["f"][p]], [o["f"][-1]]), (what, p)
+    assert len(res["tr_f"][p]) == len(o["f"]), (what, p)
+    assert same_bits(res["tr_f"][p], o["f"]), (what, p)
+    assert same_bits(res["tr_gnorm"][p], o["gnorm"]), (what, p)
+    a1, a2 = res["tr_alpha"][p], o["alpha"]
+    assert np.array_equal(np.isnan(a1), np.isnan(a2)), (what, p)
+    assert same_bits(a1[~np.isnan(a1)], a2[~np.isnan(a2)]), (what, p)
+    want = message_counts(o)
+    assert [res["events"][p][k] for k in EVENT_KEYS] == want[:4], (what, p, res["events"][p], want)
+    assert (res["status"][p] == "ls_failed") == (want[4] > 0), (what, p)
+
+
+def solve(n, m, A, b, X0, ls, maxit, tol=1e-5, launch=None):
+    with L.Batch(n, m, len(X0)) as bt:
+        if launch:
+            bt.set_launch(*launch)
+        bt.set_dense_quadratics(A, b)
+        return bt.minimize("dense", X0, ls, max_iterations=maxit, tolerance=tol, trace=True)
+
+
+# ---- 1. parity matrix on the known-answer data ------------------------------------------------
+@pytest.mark.parametrize("m", [1, 5])
+@pytest.mark.parametrize("n", [2, 3, 5, 10, 100])
+@pytest.mark.parametrize("ls", SEARCHES)
+def test_parity_matrix(ls, n, m):
+    A, b, X0 = fixture_batch(n, 3)
+    orc = oracle(("matrix", ls, n, m), A, b, X0, ls, m, 1000, 1e-5)
+    iters = [orc[p]["iters"] for p in range(3)]
+    assert all(orc[p]["status"] == "converged" for p in range(3)), (ls, n, m)  # conditions on the inputs (CPU)
+    if m == 5:
+        assert all(4 <= k <= 62 for k in iters), iters
+        assert n < 5 or len(set(iters)) >= 2, iters  # the problems of a batch end at different times
+    res = solve(n, m, A, b, X0, ls, 1000)
+    for p in range(3):
+        check_problem(res, p, orc[p], (ls, n, m))
+    assert np.abs(res["x"][0] - _data[f"minimum{n}"]).max() < 1e-4
+
+
+# ---- 2. row and segment seams ------------------------------------------------------------------
+@pytest.mark.parametrize("m", [1, 5])
+@pytest.mark.parametrize("n", [64, 65, 513])
+@pytest.mark.parametrize("ls", SEARCHES)
+def test_row_and_segment_seams(ls, n, m):
+    B = 2 if n < 513 else 1  # (the oracle takes a second per problem at n = 513)
+    A, b, X0 = spectrum_batch(n, B, np.logspace(0, 3, n), 1000 + n)
+    orc = oracle(("seams", ls, n, m), A, b, X0, ls, m, 14, 1e-5)
+    for p in range(B):  # conditions on the inputs (CPU): all 14 iterations, no guard message
+        assert orc[p]["status"] == "max_iter" and orc[p]["iters"] == 14 > m + 2, (ls, n, m, p)
+        assert message_counts(orc[p]) == [0, 0, 0, 0, 0], (ls, n, m, p, orc[p]["messages"])
+    res = solve(n, m, A, b, X0, ls, 14)
+    for p in range(B):
+        check_problem(res, p, orc[p], (ls, n, m))
+
+
+def test_largest_fixture_reaches_its_minimum():
+    n, m = 500, 5
+    A, b, X0 = fixture_batch(n, 2)
+    orc = oracle(("n500",), A, b, X0, "backtracking", m, 1000, 1e-5)
+    assert all(orc[p]["status"] == "converged" and m + 2 < orc[p]["iters"] <= 62 for p in range(2))
+    res = solve(n, m, A, b, X0, "backtracking", 1000)
+    for p in range(2):
+        check_problem(res, p, orc[p], "n=500")
+    assert np.abs(res["x"][0] - _data["minimum500"]).max() < 1e-4
+
+
+# ---- 3. guard path: an indefinite matrix skips updates ------------------------------------------
+@pytest.mark.parametrize("n", [5, 65])
+@pytest.mark.parametrize("ls", ["backtracking", "interpolation", "wolfe"])
+def test_guard_path(ls, n):
+    m, B = 3, 3
+    A, b, X0 = spectrum_batch(n, B, np.linspace(-1.0, 2.0, n), 2000 + n)
+    orc = oracle(("guard", ls, n), A, b, X0, ls, m, 12, 1e-5)
+    for p in range(B):  # conditions on the inputs (CPU)
+        assert message_counts(orc[p])[1] > 0, (ls, n, p, orc[p]["messages"])
+        assert np.isfinite(orc[p]["f"]).all() and np.isfinite(orc[p]["x"]).all(), (ls, n, p)
+    res = solve(n, m, A, b, X0, ls, 12)
+    for p in range(B):
+        check_problem(res, p, orc[p], ("guard", ls, n))
+        assert res["events"][p]["skipped_updates"] == message_counts(orc[p])[1] > 0
+
+
+# ---- 4. the same as the single-problem path, counters included -----------------------------------
+@pytest.mark.parametrize("ls", SEARCHES)
+def test_same_as_single_problem_path(ls):
+    n, m, B = 100, 5, 3
+    A, b, X0 = fixture_batch(n, B)
+    res = solve(n, m, A, b, X0, ls, 1000)
+    with L.Context(n, m) as c:
+        for p in range(B):
+            c.set_dense_quadratic(A[p], b[p])
+            one = c.minimize("dense", X0[p], ls, max_iterations=1000, tolerance=1e-5, trace=True)
+            assert same_bits(res["x"][p], one["x"]), (ls, p)
+            assert same_bits([res["f"][p], res["gnorm"][p]], [one["f"], one["gnorm"]]), (ls, p)
+            assert res["iterations"][p] == one["iterations"] and res["status"][p] == one["status"], (ls, p)
+            for k in ("trials_f", "trials_fg", "commits", "h_min", "h_max"):
+                assert res[k][p] == one[k], (ls, p, k, res[k][p], one[k])
+            assert same_bits(res["tr_f"][p], one["tr_f"]) and same_bits(res["tr_gnorm"][p], one["tr_gnorm"]), (ls, p)
+
+
+# ---- 5. launch shape does not matter -------------------------------------------------------------
+def test_launch_shape_does_not_matter():
+    n, m, B = 10, 3, 6
+    A, b, X0 = fixture_batch(n, B)
+    orc = oracle(("shape",), A, b, X0, "wolfe", m, 1000, 1e-5)
+    assert len(set(orc[p]["iters"] for p in range(B))) >= 3  # a condition on the inputs (CPU)
+    for launch in [(1, 1), (2, 3), (0, 64)]:
+        res = solve(n, m, A, b, X0, "wolfe", 1000, launch=launch)
+        for p in range(B):
+            check_problem(res, p, orc[p], ("shape", launch))
+
+
+# ---- 6. more problems than workgroups, and indexing ----------------------------------------------
+def test_more_problems_than_workgroups():
+    n, m, B, period = 5, 2, 600, 75
+    A, b, X0 = fixture_batch(n, B, period)
+    spot = [0, 1, 74, 75, 299, 300, 598, 599]
+    orc = oracle(("B600",), A, b, X0, "backtracking", m, 1000, 1e-5, problems=spot)
+    res = solve(n, m, A, b, X0, "backtracking", 1000, launch=(2, 0))
+    for p in spot:
+        check_problem(res, p, orc[p], "B=600")
+    for p in range(period, B):  # the data repeat: the same bits as the problem one period back
+        q = p - period
+        assert same_bits(res["x"][p], res["x"][q]) and same_bits(res["tr_f"][p], res["tr_f"][q]), p
+        assert same_bits(res["tr_alpha"][p], res["tr_alpha"][q]) and res["iterations"][p] == res["iterations"][q], p
+    assert len(set(res["iterations"][:period])) >= 3 and len(set(bits(res["f"][:period]))) == period
+
+
+# ---- 7. one matrix shared by every problem -------------------------------------------------------
+@pytest.mark.parametrize("ls", ["backtracking", "wolfe"])
+def test_shared_matrix(ls):
+    n, m, B = 10, 5, 4
+    A, b, X0 = fixture_batch(n, B)
+    one = np.ascontiguousarray(A[1])
+    shared = solve(n, m, one, b, X0, ls, 1000)
+    replicated = solve(n, m, np.stack([one] * B), b, X0, ls, 1000)
+    orc = oracle(("shared", ls), one, b, X0, ls, m, 1000, 1e-5)
+    for p in range(B):
+        check_problem(shared, p, orc[p], ("shared", ls))
+        for k in ("x", "f", "gnorm", "iterations", "trials_f", "trials_fg", "commits"):
+            assert same_bits(np.asarray(shared[k][p], np.float64), np.asarray(replicated[k][p], np.float64)), (k, p)
+
+
+# ---- 8. data replaced between solves; the stencil objectives still work --------------------------
+def test_data_replaced_between_solves():
+    n, m, B = 10, 3, 3
+    A1, b1, X0 = fixture_batch(n, B)
+    A2, b2 = A1[::-1] + 0.5 * np.eye(n), 2.0 * b1[::-1]
+    fresh = solve(n, m, A2, b2, X0, "interpolation", 1000)
+    sep = O.x0_uniform(n, 7, -2.0, 2.0)
+    with L.Batch(n, m, B) as bt:
+        bt.set_dense_quadratics(A1, b1)
+        first = bt.minimize("dense", X0, "interpolation", trace=True)
+        bt.set_dense_quadratics(A2[0], b2)  # shared, then per problem again: the matrix store grows back
+        bt.set_dense_quadratics(A2, b2)
+        second = bt.minimize("dense", X0, "interpolation", trace=True)
+        stencil = bt.minimize("quad_sep", np.stack([sep] * B), "backtracking", max_iterations=6, trace=True)
+    orc1 = oracle(("replace", 1), A1, b1, X0, "interpolation", m, 1000, 1e-5)
+    orc2 = oracle(("replace", 2), A2, b2, X0, "interpolation", m, 1000, 1e-5)
+    o3 = O.lbfgs("quad_sep", sep, "backtracking", m, 6, 1e-5, mode=O.CANON)
+    for p in range(B):
+        check_problem(first, p, orc1[p], "first data")
+        check_problem(second, p, orc2[p], "second data")
+        for k in ("x", "f", "gnorm", "iterations", "trials_f", "trials_fg", "commits"):
+            assert same_bits(np.asarray(second[k][p], np.float64), np.asarray(fresh[k][p], np.float64)), (k, p)
+        assert stencil["status"][p] == o3["status"] and stencil["iterations"][p] == o3["iters"]
+        assert same_bits(stencil["x"][p], o3["x"]) and same_bits(stencil["tr_f"][p], o3["f"])
+
+
+# ---- 9. refusals ---------------------------------------------------------------------------------
+def test_refusals():
+    n, m, B = 5, 2, 3
+    A, b, X0 = fixture_batch(n, B)
+    orc = oracle(("refuse",), A, b, X0, "backtracking", m, 1000, 1e-5)
+    with L.Batch(n, m, B) as bt:
+        def refused(**kw):
+            args = dict(objective="dense", X0=X0, line_search="backtracking", max_iterations=1000)
+            args.update(kw)
+            with pytest.raises(L.LbfgsError) as e:
+                bt.minimize(**args)
+            assert e.value.rc == -1, kw
+
+        refused()  # no data yet
+        res = bt.minimize("quad_sep", X0, "backtracking", max_iterations=4)  # still a working batch
+        assert list(res["iterations"]) == [O.lbfgs("quad_sep", x, "backtracking", m, 4, 1e-5, mode=O.CANON)["iters"]
+                                           for x in X0]
+        for bad_A, bad_b, exc in [(A[:2], b, ValueError), (A[:, :4, :4], b, ValueError), (A, b[:, :4], ValueError),
+                                  (A.astype(np.float32), b, TypeError), (A, b.astype(np.float32), TypeError)]:
+            with pytest.raises(exc):
+                bt.set_dense_quadratics(bad_A, bad_b)
+        refused()  # a refused setter sets nothing
+        bt.set_dense_quadratics(A, b)
+        refused(objective="host")
+        for flag in (L.FLAG_VERBOSE, L.FLAG_UNFUSED, L.FLAG_VECTOR_FREE, L.FLAG_REFERENCE_CALLS,
+                     L.FLAG_CUDA_COMPAT, L.FLAG_CUDA_VARIANT):
+            refused(flags=flag)
+        res = bt.minimize("dense", X0, "backtracking", trace=True)
+        for p in range(B):
+            check_problem(res, p, orc[p], "after refusals")
+    big = L.DENSE_BATCH_NMAX + 1
+    with L.Batch(big, 1, 1) as bt:  # a batch the stencil objectives can use, over the dense limit
+        with pytest.raises(L.LbfgsError) as e:
+            bt.set_dense_quadratics(np.eye(big), np.zeros((1, big)))
+        assert e.value.rc == -1
+        x0 = O.x0_uniform(big, 1, -2.0, 2.0)[None, :]
+        with pytest.raises(L.LbfgsError) as e:
+            bt.minimize("dense", x0, "backtracking", max_iterations=2)
+        assert e.value.rc == -1
+        res = bt.minimize("quad_sep", x0, "backtracking", max_iterations=2)
+        o = O.lbfgs("quad_sep", x0[0], "backtracking", 1, 2, 1e-5, mode=O.CANON)
+        assert same_bits(res["x"][0], o["x"]) and res["iterations"][0] == o["iters"]
