@@ -83,6 +83,7 @@ int lbk_geometry_plan(int64_t n, int rank, int world, lbk_geo* out) {
 }
 
 static int rccl_init(lbk_ctx* c, const void* nccl_id);
+static int persist_grid(const lbk_ctx* c);
 
 int lbk_create(lbk_ctx** out, int device, int64_t n, int rank, int world, const void* nccl_id, lbk_group* grp) {
     *out = nullptr;
@@ -380,6 +381,18 @@ int lbk_create(lbk_ctx** out, int device, int64_t n, int rank, int world, const 
         c->coop_max = 0;
         c->wolfe_max = 0;
     }
+    // LBFGS_STORE_G: unset, the TWOLOOP commit of a built-in objective leaves g_new
+    // unstored where that pays - one rank, the launch sequence (not the cooperative iteration, whose
+    // launch reads g), no persistent two-loop (it would have g stored every iteration); 1: always
+    // store; poison: as unset, and an unstored gradient's buffer is filled with NaN (tests: a reader
+    // that was missed shows up in a bit-compare)
+    c->ug_on = world == 1 && !grp && !nccl_id && !(c->coop_max > 0 && G.nseg <= c->coop_max) && persist_grid(c) == 0;
+    if (const char* e = getenv("LBFGS_STORE_G")) {
+        if (!strcmp(e, "poison"))
+            c->ug_poison = 1;
+        else if (atoi(e) != 0)
+            c->ug_on = 0;
+    }
     if (!grp && nccl_id) return rccl_init(c, nccl_id);
     return 0;
 }
@@ -598,6 +611,9 @@ double* lbk_vec_alloc(lbk_ctx* c) {
 }
 
 void lbk_vec_free(lbk_ctx* c, double* v) {
+    if (c)
+        for (auto& e : c->ug)
+            if (e.g && (e.g == v || e.x == v)) e.g = nullptr;
     if (!v) return;
     void* base = v - LBK_FRONT;
     VecPool& P = vec_pool();
@@ -773,6 +789,7 @@ void xfer_pool_free(lbk_ctx* c) {
 }
 
 int lbk_upload(lbk_ctx* c, double* dst, const double* host_global) {
+    if (const int rc_ = ug_flush(c)) return rc_;
     // local range plus the ghosts that exist globally
     const int64_t lo = c->geo.elem_lo > 0 ? c->geo.elem_lo - 1 : 0;
     const int64_t hi = std::min<int64_t>(c->geo.elem_lo + c->geo.n_loc + 1, c->geo.n);
@@ -781,6 +798,7 @@ int lbk_upload(lbk_ctx* c, double* dst, const double* host_global) {
 }
 
 int lbk_upload_local(lbk_ctx* c, double* dst, const double* host_local) {
+    if (const int rc_ = ug_flush(c)) return rc_;
     if (c->geo.n_loc == 0) return 0;
     HIPCHK(c, hipMemcpyAsync(dst, host_local, sizeof(double) * c->geo.n_loc, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -790,6 +808,7 @@ int lbk_upload_local(lbk_ctx* c, double* dst, const double* host_local) {
 // asynchronous transfers of the local range on the solver stream; event `tag` (0..3) marks the
 // copy's completion for lbk_xfer_wait (host-callback objectives: double-buffered pinned buffers)
 int lbk_download_local_async(lbk_ctx* c, double* host_local, const double* src, int tag) {
+    if (const int rc_ = ug_in(c, src)) return rc_;
     if (tag < 0 || tag >= 4) return -1;
     if (!c->xfer_ev[tag]) HIPCHK(c, hipEventCreateWithFlags(&c->xfer_ev[tag], hipEventDisableTiming));
     if (c->geo.n_loc > 0)
@@ -799,6 +818,7 @@ int lbk_download_local_async(lbk_ctx* c, double* host_local, const double* src, 
 }
 
 int lbk_upload_local_async(lbk_ctx* c, double* dst, const double* host_local, int tag) {
+    if (const int rc_ = ug_flush(c)) return rc_;
     if (tag < 0 || tag >= 4) return -1;
     if (!c->xfer_ev[tag]) HIPCHK(c, hipEventCreateWithFlags(&c->xfer_ev[tag], hipEventDisableTiming));
     if (c->geo.n_loc > 0)
@@ -818,11 +838,13 @@ int lbk_download(lbk_ctx* c, double* host_global, const double* src) {
 }
 
 int lbk_download_local(lbk_ctx* c, double* host_local, const double* src) {
+    if (const int rc_ = ug_in(c, src)) return rc_;
     if (c->geo.n_loc == 0) return 0;
     return xfer(c, host_local, src, sizeof(double) * c->geo.n_loc, false);
 }
 
 int lbk_copy(lbk_ctx* c, double* dst, const double* src) {
+    if (const int rc_ = ug_flush(c)) return rc_;
     HIPCHK(c, hipMemcpyAsync(dst - 1, src - 1, sizeof(double) * (c->geo.n_loc + 2), hipMemcpyDeviceToDevice,
                              c->stream));
     return 0;
@@ -830,6 +852,8 @@ int lbk_copy(lbk_ctx* c, double* dst, const double* src) {
 
 
 int lbk_dot(lbk_ctx* c, const double* a, const double* b, int slot) {
+    if (const int rc_ = ug_in(c, a)) return rc_;
+    if (const int rc_ = ug_in(c, b)) return rc_;
     Geo g = kgeo(c);
     Red r = kred_deferrable(c, slot);
     fold_producer(c, r, false);
@@ -843,12 +867,27 @@ int lbk_dot(lbk_ctx* c, const double* a, const double* b, int slot) {
 
 int lbk_axpy_dot(lbk_ctx* c, double* qout, const double* qin, const double* y, const double* s, double rho,
                  int ref_alpha, int slot) {
+    // q_in an unstored gradient: the pass forms it from its x (entries exist on one rank only)
+    const int ui = ug_find(c, qin);
+    const bool from_x = ui >= 0 && !c->ug[ui].stored && c->ug[ui].x != qout;
+    const double* ux = from_x ? c->ug[ui].x : nullptr;
+    const int uobj = from_x ? c->ug[ui].obj : 0;
+    if (!from_x)
+        if (const int rc_ = ug_in(c, qin)) return rc_;
+    if (const int rc_ = ug_in(c, y)) return rc_;
+    if (const int rc_ = ug_in(c, s)) return rc_;
+    if (const int rc_ = ug_out(c, {qout})) return rc_;
     Geo g = kgeo(c);
     g.ppart = take_pending(c, ref_alpha);
     const FoldSrc fs = take_fold(c, ref_alpha);
     Red r = kred_deferrable(c, slot);
     fold_producer(c, r, false);
     const double* pa = sref(c, ref_alpha);
+    if (from_x)
+        return launch(c, LBK_K_AXPY_DOT, 4, slot, [&] {
+            OBJ_DISPATCH(uobj, hipLaunchKernelGGL((k_axpy_dot_x<O_, NT_>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, qout, ux, y, s, rho, pa, g, r));
+            return 0;
+        });
     return launch(c, LBK_K_AXPY_DOT, 4, slot, [&] {
         if (r.fp.peers || fs.mbx)
             NT_DISPATCH(c, hipLaunchKernelGGL((k_axpy_dot<NT_, true>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, qout, qin, y, s, rho, pa, g, r, fs));
@@ -859,6 +898,9 @@ int lbk_axpy_dot(lbk_ctx* c, double* qout, const double* qin, const double* y, c
 
 int lbk_mid(lbk_ctx* c, double* rout, const double* qin, const double* y0, double rho0, double gamma,
             int ref_alpha, int slot) {
+    if (const int rc_ = ug_in(c, qin)) return rc_;
+    if (const int rc_ = ug_in(c, y0)) return rc_;
+    if (const int rc_ = ug_out(c, {rout})) return rc_;
     Geo g = kgeo(c);
     g.ppart = take_pending(c, ref_alpha);
     const FoldSrc fs = take_fold(c, ref_alpha);
@@ -876,6 +918,10 @@ int lbk_mid(lbk_ctx* c, double* rout, const double* qin, const double* y0, doubl
 
 int lbk_axpy2_dot(lbk_ctx* c, double* rr, const double* rin, const double* s, const double* ynext, double rho,
                   int ref_beta, int ref_alpha, int slot) {
+    if (const int rc_ = ug_in(c, rin)) return rc_;
+    if (const int rc_ = ug_in(c, s)) return rc_;
+    if (const int rc_ = ug_in(c, ynext)) return rc_;
+    if (const int rc_ = ug_out(c, {rr})) return rc_;
     Geo g = kgeo(c);
     g.ppart = take_pending(c, ref_beta);
     const FoldSrc fs = take_fold(c, ref_beta);
@@ -894,6 +940,10 @@ int lbk_axpy2_dot(lbk_ctx* c, double* rr, const double* rin, const double* s, co
 
 int lbk_last(lbk_ctx* c, double* dout, const double* rr, const double* s, const double* gg, double rho,
              int ref_beta, int ref_alpha, int slot) {
+    if (const int rc_ = ug_in(c, rr)) return rc_;
+    if (const int rc_ = ug_in(c, s)) return rc_;
+    if (const int rc_ = ug_in(c, gg)) return rc_;
+    if (const int rc_ = ug_out(c, {dout})) return rc_;
     Geo g = kgeo(c);
     g.ppart = take_pending(c, ref_beta);
     Red r = kred(c, slot);
@@ -906,6 +956,8 @@ int lbk_last(lbk_ctx* c, double* dout, const double* rr, const double* s, const 
 }
 
 int lbk_negdot(lbk_ctx* c, double* dout, const double* gg, int slot) {
+    if (const int rc_ = ug_in(c, gg)) return rc_;
+    if (const int rc_ = ug_out(c, {dout})) return rc_;
     Geo g = kgeo(c);
     Red r = kred(c, slot);
     if (c->geo.world > 1) g.edge_slot = r.slot;
@@ -916,10 +968,32 @@ int lbk_negdot(lbk_ctx* c, double* dout, const double* gg, int slot) {
 
 
 int lbk_eval(lbk_ctx* c, int obj, const double* x, double* gout, int slot) {
+    if (const int rc_ = ug_in(c, x)) return rc_;
+    if (const int rc_ = ug_out(c, {gout})) return rc_;
     Geo g = kgeo(c);
     Red r = kred(c, slot, 2);
     DirArgs da = {nullptr, nullptr, nullptr, 0.0, nullptr, nullptr, 0.0, nullptr, c->geo.g_lo, c->geo.g_hi};
-    return launch(c, LBK_K_EVAL, gout ? 2 : 1, slot, [&] {
+    const int rc = launch(c, LBK_K_EVAL, gout ? 2 : 1, slot, [&] {
+        OBJ_DISPATCH(obj, hipLaunchKernelGGL((k_objective<O_, true, true, NT_>), dim3(nblocks(c)), dim3(LB_BLOCK), 0,
+                                             c->stream, x, da, 0.0, gout, g, r));
+        return 0;
+    }, 2);
+    if (rc == 0 && gout && gout != x) ug_record(c, gout, x, obj, 1);  // gout holds grad f(x)
+    return rc;
+}
+
+// Stores unstored gradient i into its buffer: the evaluation at its x (k_objective's gradient is
+// the commit's, obj_grad on the same operands), f and g.g into a scratch slot nothing reads.
+int lbk_ug_materialise(lbk_ctx* c, int i) {
+    lbk_ctx::Ug& e = c->ug[i];
+    e.stored = 1;
+    const double* x = e.x;
+    double* gout = e.g;
+    const int obj = e.obj;
+    Geo g = kgeo(c);
+    Red r = kred(c, LBK_UG_SLOT, 2);
+    DirArgs da = {nullptr, nullptr, nullptr, 0.0, nullptr, nullptr, 0.0, nullptr, c->geo.g_lo, c->geo.g_hi};
+    return launch(c, LBK_K_EVAL, 2, LBK_UG_SLOT, [&] {
         OBJ_DISPATCH(obj, hipLaunchKernelGGL((k_objective<O_, true, true, NT_>), dim3(nblocks(c)), dim3(LB_BLOCK), 0,
                                              c->stream, x, da, 0.0, gout, g, r));
         return 0;
@@ -927,6 +1001,9 @@ int lbk_eval(lbk_ctx* c, int obj, const double* x, double* gout, int slot) {
 }
 
 int lbk_trial(lbk_ctx* c, int obj, const double* x, const double* d, double alpha, double* gout, int slot) {
+    if (const int rc_ = ug_in(c, x)) return rc_;
+    if (const int rc_ = ug_in(c, d)) return rc_;
+    if (const int rc_ = ug_out(c, {gout})) return rc_;
     Geo g = kgeo(c);
     Red r = kred(c, slot, 2);
     DirArgs da = {d, nullptr, nullptr, 0.0, nullptr, nullptr, 0.0, ghost_ptr(c), c->geo.g_lo, c->geo.g_hi};
@@ -963,6 +1040,8 @@ int lbk_dense_set(lbk_ctx* c, const double* A, const double* b) {
 }
 
 int lbk_dense_eval(lbk_ctx* c, const double* x, double* gout, int slot) {
+    if (const int rc_ = ug_in(c, x)) return rc_;
+    if (const int rc_ = ug_out(c, {gout})) return rc_;
     if (!c->dq_A) {
         snprintf(c->err, sizeof c->err, "dense quadratic: no matrix (lbfgs_set_dense_quadratic)");
         return -1;
@@ -981,6 +1060,9 @@ int lbk_dense_eval(lbk_ctx* c, const double* x, double* gout, int slot) {
 }
 
 int lbk_point(lbk_ctx* c, double* z, const double* x, const double* d, double alpha) {
+    if (const int rc_ = ug_in(c, x)) return rc_;
+    if (const int rc_ = ug_in(c, d)) return rc_;
+    if (const int rc_ = ug_out(c, {z})) return rc_;
     const int64_t lo = -1, hi = c->geo.n_loc + 1;
     const int64_t cnt = hi - lo;
     const int nb = (int)((cnt + 255) / 256);
@@ -990,6 +1072,9 @@ int lbk_point(lbk_ctx* c, double* z, const double* x, const double* d, double al
 }
 
 int lbk_elementwise(lbk_ctx* c, int op, double* out, const double* a, const double* b, double alpha) {
+    if (const int rc_ = ug_in(c, a)) return rc_;
+    if (const int rc_ = ug_in(c, b)) return rc_;
+    if (const int rc_ = ug_out(c, {out})) return rc_;
     const int nb = (int)std::min<int64_t>((c->geo.n_loc + 255) / 256, 4096);
     return launch(c, LBK_K_POINT, op == 1 || op == 3 ? 3 : 2, -1, [&] {
         if (nb > 0) hipLaunchKernelGGL(k_elementwise, dim3(nb), dim3(256), 0, c->stream, op, out, a, b, alpha, c->geo.n_loc);
@@ -1014,6 +1099,12 @@ int lbk_twoloop_ok(const lbk_ctx* c, int h) { return h >= 1 && h <= LBK_SMALL_HM
 int lbk_twoloop_persist(lbk_ctx* c, int h, const double* g, double* q, double* r, const double* const* S,
                         const double* const* Y, const double* rho, double gamma, int p0_ref, int slot_p0,
                         int slot_a0, int slot_b0) {
+    if (const int rc_ = ug_in(c, g)) return rc_;
+    for (int i_ = 0; i_ < h; ++i_) {
+        if (const int rc_ = ug_in(c, S[i_])) return rc_;
+        if (const int rc_ = ug_in(c, Y[i_])) return rc_;
+    }
+    if (const int rc_ = ug_out(c, {q, r})) return rc_;
     const int nb = lbk_twoloop_ok(c, h) ? persist_grid(c) : 0;
     if (!nb) return -1;
     // p0_ref's slot is read directly (slot_total) by the kernel: a stage 2 still pending for it
@@ -1067,6 +1158,13 @@ int lbk_small_iter(lbk_ctx* c, int obj, int h, const double* g, double* q, doubl
                    const double* const* Y, const double* rho, double gamma, int p0_ref, double a0, const double* x,
                    double* xn, double* gn, double* so, double* yo, int slot_p0, int slot_a0, int slot_b0,
                    int slot_c, double cand, const lbk_spec* spec, unsigned long long* epoch) {
+    if (const int rc_ = ug_in(c, g)) return rc_;
+    for (int i_ = 0; i_ < h; ++i_) {
+        if (const int rc_ = ug_in(c, S[i_])) return rc_;
+        if (const int rc_ = ug_in(c, Y[i_])) return rc_;
+    }
+    if (const int rc_ = ug_in(c, x)) return rc_;
+    if (const int rc_ = ug_out(c, {q, r, xn, gn, so, yo})) return rc_;
     if (epoch) *epoch = 0;
     if (!lbk_small_ok(c, h) || (spec && !lbk_small_spec_ok(c, h))) return -1;
     SmallArgs a;
@@ -1163,6 +1261,12 @@ static int small_wait(lbk_ctx* c, unsigned long long epoch, int word = 0);
 
 int lbk_search_dev(lbk_ctx* c, int obj, int ls, const double* x, const double* d, lbk_search* st,
                    const lbk_search_commit* cm) {
+    if (const int rc_ = ug_in(c, x)) return rc_;
+    if (const int rc_ = ug_in(c, d)) return rc_;
+    if (cm) {
+        if (const int rc_ = ug_in(c, cm->g)) return rc_;
+        if (const int rc_ = ug_out(c, {cm->xn, cm->gn, cm->so, cm->yo})) return rc_;
+    }
     if (!lbk_search_dev_ok(c, obj) || ls < 0 || ls > 3 || (cm && cm->slot >= 0 && (cm->slot >= LBK_NSLOTS || !cm->g))) {
         snprintf(c->err, sizeof c->err, "lbk_search_dev: not a single-rank cooperative size (or bad arguments)");
         return -1;
@@ -1379,6 +1483,9 @@ int lbk_small_ok(const lbk_ctx* c, int h) {
 
 int lbk_update(lbk_ctx* c, int op, double* out, const double* a, const double* b, double rho, int slot_a,
                int slot_b, double scal) {
+    if (const int rc_ = ug_in(c, a)) return rc_;
+    if (const int rc_ = ug_in(c, b)) return rc_;
+    if (const int rc_ = ug_out(c, {out})) return rc_;
     const int64_t npair = c->geo.n_loc / 2;
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((npair + 255) / 256, 16384));
     const double* pa = slot_a >= 0 ? c->slots + (int64_t)slot_a * LBK_SLOT : nullptr;
@@ -1413,6 +1520,7 @@ int lbk_update(lbk_ctx* c, int op, double* out, const double* a, const double* b
 }
 
 int lbk_checksum(lbk_ctx* c, const double* x, uint64_t* c1, uint64_t* c2) {
+    if (const int rc_ = ug_in(c, x)) return rc_;
     HIPCHK(c, hipMemsetAsync(c->d_ck, 0, 2 * sizeof(unsigned long long), c->stream));
     if (c->geo.n_loc > 0) {
         int nb = (int)std::min<int64_t>((c->geo.n_loc + 255) / 256, 2048);
@@ -1601,6 +1709,7 @@ int lbk_coop_info(const lbk_ctx* c, int* coop_max, int* search_max, int* fallbac
 
 int lbk_stream_probe(lbk_ctx* c, double* q, const double* const* ys, const double* const* ss, int npairs,
                      int launches, double* us, int variant, double* const* outs) {
+    if (const int rc_ = ug_out(c, {q})) return rc_;
     if (launches < 1 || !us || !q || !ys || !ss || npairs < 1) return -1;
     for (int k = 0; k < npairs; ++k)
         if (!ys[k] || !ss[k]) return -1;

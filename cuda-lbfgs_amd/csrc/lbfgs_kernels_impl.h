@@ -45,6 +45,7 @@
 #include <unistd.h>
 #include <cstring>
 #include <ctime>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
@@ -1364,6 +1365,20 @@ __device__ __forceinline__ double2 objective_pair(double2 z, double zh, int64_t 
     return g;
 }
 
+// gradient of the two elements of a lane at z, formed as objective_pair forms it (the same operands
+// and operations, so the same bits) without the f terms: a pass that holds x recomputes the
+// gradient a commit or an evaluation at x would have stored (unstored gradients)
+template <int OBJ>
+__device__ __forceinline__ double2 grad_pair(double2 z, double zh, int64_t e0, int64_t n) {
+    const int lane = threadIdx.x & 63;
+    const Nb nb = neighbours(z.x, z.y, zh, lane);
+    const bool p0 = e0 + 1 < n, p1 = e0 + 2 < n;
+    double2 g;
+    g.x = obj_grad<OBJ>(nb.l, z.x, z.y, e0 > 0, p0);
+    g.y = obj_grad<OBJ>(z.x, z.y, nb.r, true, p1);
+    return g;
+}
+
 // Evaluate f (and optionally g) at z = x (NO_DIR, reductions f, g.g; lbfgs.cpp:29-30) or at
 // z = x + alpha d (reductions f, g_t . d; line_search.cpp trials).
 template <int OBJ, bool NO_DIR, bool WITH_G, bool NT>
@@ -1410,8 +1425,12 @@ __global__ __launch_bounds__(LB_BLOCK) void k_objective(const double* __restrict
 //   [GD] g.d  [F] f  [SY] s.y  [YY] y.y  [GG] g_new.g_new  [SG] s.g_new  [DPHI] g_new.d
 // CAND: also f(x + cand d) at the line search's next backtracking step [FC] (no extra bytes:
 // x and d are in registers), so a rejected first step needs no trial pass for the second.
-template <int OBJ, int DMODE, bool NT, bool CAND = false>
+// UG (TWOLOOP, built-in objectives): the gradient vectors are not touched. g = grad f(x) is formed
+// from the row's x and its x halo - the doubles the commit or evaluation at x computed - and g_new
+// is not stored (the device layer's table of unstored gradients, lbk_commit): 3 R + 3 W.
+template <int OBJ, int DMODE, bool NT, bool CAND = false, bool UG = false>
 struct OpCommit {
+    static_assert(!UG || (DMODE == LBK_D_TWOLOOP && OBJ != LBK_OBJ_NONE), "UG: TWOLOOP, built-in objectives");
     static constexpr int K = CAND ? 8 : 7;
     const double* __restrict__ x;
     DirArgs da;
@@ -1424,12 +1443,12 @@ struct OpCommit {
     double cand;
     struct Row {
         double2 x, g, d, z, gx;
-        double zh, zch;
+        double zh, zch, xh;
     };
     static constexpr bool kStencil = OBJ != LBK_OBJ_NONE && (OBJ == LBK_OBJ_ROSENBROCK || OBJ == LBK_OBJ_QUAD_TRIDIAG);
     __device__ void load_core(Row& r, int64_t i) const {
         r.x = ldv<NT>(x + i);
-        r.g = ldv<NT>(da.g + i);
+        r.g = UG ? make_double2(0.0, 0.0) : ldv<NT>(da.g + i);
         r.d = load_dir<DMODE, NT>(da, i, r.g);
         if (OBJ == LBK_OBJ_NONE) r.gx = ldv<NT>(gn + i);
         r.z.x = r.x.x + alpha * r.d.x;
@@ -1441,24 +1460,27 @@ struct OpCommit {
     __device__ void set_halo(Row& r, double2 xd) const {
         r.zh = xd.x + alpha * xd.y;
         if (CAND) r.zch = xd.x + cand * xd.y;
+        if (UG) r.xh = xd.x;
     }
     __device__ void load(Row& r, int64_t i) const {
         r.x = ldv<NT>(x + i);
-        r.g = ldv<NT>(da.g + i);
+        r.g = UG ? make_double2(0.0, 0.0) : ldv<NT>(da.g + i);
         r.d = load_dir<DMODE, NT>(da, i, r.g);
         if (OBJ == LBK_OBJ_NONE) r.gx = ldv<NT>(gn + i);
         r.z.x = r.x.x + alpha * r.d.x;
         r.z.y = r.x.y + alpha * r.d.y;
-        if (CAND) {
+        if (CAND || UG) {  // (halo_z's operands and operations)
             const double2 xd = halo_xd<OBJ, DMODE>(x, da, i, n_loc);
             r.zh = xd.x + alpha * xd.y;
-            r.zch = xd.x + cand * xd.y;
+            if (CAND) r.zch = xd.x + cand * xd.y;
+            if (UG) r.xh = xd.x;
         } else {
             r.zh = (OBJ == LBK_OBJ_NONE) ? 0.0 : halo_z<OBJ, false, DMODE>(x, da, alpha, i, n_loc);
         }
     }
     template <bool MASK>
     __device__ void apply(Row& r, int64_t i, int64_t e0, bool v0, bool v1, double (&acc)[K]) const {
+        if constexpr (UG) r.g = grad_pair<OBJ>(r.x, r.xh, e0, n);
         if (CAND) {
             double2 zc;
             zc.x = r.x.x + cand * r.d.x;
@@ -1470,7 +1492,7 @@ struct OpCommit {
             g2 = r.gx;
         } else {
             g2 = objective_pair<OBJ, MASK>(r.z, r.zh, e0, n, v0, v1, acc[LBK_C_F], true);
-            st2<MASK, NT>(gn + i, g2, v0, v1);
+            if (!UG) st2<MASK, NT>(gn + i, g2, v0, v1);
         }
         st2<MASK, NT>(xn + i, r.z, v0, v1);
         double2 sv, yv;
@@ -1491,7 +1513,7 @@ struct OpCommit {
 
 // No waves-per-SIMD attribute: asking the register allocation for 4 waves spills 82 VGPRs (DESIGN.md,
 // round-6 table item 2); the compile-time switch for it was removed.
-template <int OBJ, int DMODE, bool NT, bool CAND = false>
+template <int OBJ, int DMODE, bool NT, bool CAND = false, bool UG = false>
 __global__ __launch_bounds__(LB_BLOCK) void k_commit(const double* __restrict__ x, DirArgs da, double alpha,
                                                      double* __restrict__ xn, double* __restrict__ gn,
                                                      double* __restrict__ so, double* __restrict__ yo,
@@ -1521,8 +1543,64 @@ __global__ __launch_bounds__(LB_BLOCK) void k_commit(const double* __restrict__ 
             so[e] = z - x[e];
         }
     }
-    using Op = OpCommit<OBJ, DMODE, NT, CAND>;
+    using Op = OpCommit<OBJ, DMODE, NT, CAND, UG>;
     run_pass_halo<Op, Op::K>(Op{x, da, alpha, xn, gn, so, yo, geo.n, geo.n_loc, cand}, geo, red);
+}
+
+// The first first-loop pass when g is an unstored gradient: q = grad f(x) - alpha y, s . q, the
+// gradient formed from x (grad_pair) instead of read. x's row halos travel through stream_stencil's
+// LDS edge table (the pair's second component is unused); the canonical order and the cache
+// policies are k_axpy_dot's: x, y and s stream, q is a work vector. 3 R + 1 W as k_axpy_dot.
+template <int OBJ, bool NT>
+struct OpAxpyDotX {
+    double* qout;
+    const double* __restrict__ x;
+    const double* __restrict__ y;
+    const double* __restrict__ s;
+    double alpha;
+    int64_t n, n_loc;
+    struct Row {
+        double2 x, y, s;
+        double xh;
+    };
+    static constexpr bool kStencil = OBJ == LBK_OBJ_ROSENBROCK || OBJ == LBK_OBJ_QUAD_TRIDIAG;
+    __device__ void load_core(Row& r, int64_t i) const {
+        r.x = ldv<NT>(x + i);
+        r.y = ldv<NT>(y + i);
+        r.s = ldv<NT>(s + i);
+    }
+    __device__ double2 halo_mem(int64_t hi) const {
+        return (hi < -1 || hi > n_loc) ? make_double2(0.0, 0.0) : make_double2(x[hi], 0.0);
+    }
+    __device__ double2 edge_first(const Row& r) const { return make_double2(r.x.x, 0.0); }
+    __device__ double2 edge_last(const Row& r) const { return make_double2(r.x.y, 0.0); }
+    __device__ void set_halo(Row& r, double2 xd) const { r.xh = xd.x; }
+    __device__ void load(Row& r, int64_t i) const {
+        load_core(r, i);
+        r.xh = 0.0;
+        if (needs_halo<OBJ>()) {
+            const int lane = threadIdx.x & 63;
+            if (lane == 0 || lane == 63) r.xh = halo_mem(lane == 0 ? i - 1 : i + 2).x;
+        }
+    }
+    template <bool MASK>
+    __device__ void apply(Row& r, int64_t i, int64_t e0, bool v0, bool v1, double (&acc)[1]) const {
+        const double2 g = grad_pair<OBJ>(r.x, r.xh, e0, n);
+        double2 qn;
+        qn.x = g.x - alpha * r.y.x;
+        qn.y = g.y - alpha * r.y.y;
+        st2w<MASK>(qout + i, qn, v0, v1);
+        acc[0] = fma2<MASK>(r.s, qn, acc[0], v0, v1);
+    }
+};
+
+template <int OBJ, bool NT>
+__global__ __launch_bounds__(LB_BLOCK) void k_axpy_dot_x(double* qout, const double* __restrict__ x,
+                                                         const double* __restrict__ y, const double* __restrict__ sv,
+                                                         double rho, const double* __restrict__ prev, Geo geo, Red red) {
+    const double alpha = rho * src_total(prev, geo);
+    using Op = OpAxpyDotX<OBJ, NT>;
+    run_pass_halo<Op, 1>(Op{qout, x, y, sv, alpha, geo.n, geo.n_loc}, geo, red);
 }
 
 // Batched line-search trials: f at NC steps a[0..NC-1] along d (d per DMODE: a buffer, -g, or the
@@ -3029,9 +3107,79 @@ struct lbk_ctx {
     // LBFGS_CU_PARTITION (sharded, tests and one-card rehearsals): the solver stream runs on this
     // rank's own cu_count CUs, disjoint from every other rank's, as if each rank had a GPU
     int cu_part, cu_count;
+    // Unstored gradients (LBFGS_STORE_G). For the built-in objectives the gradient is a
+    // pure function of x, so the TWOLOOP commit of the launch sequence neither reads g nor stores
+    // g_new: ug[] lists the buffers known to hold - or, `stored` 0, that would hold - grad f(x) of
+    // objective `obj` at the vector x (at most two: the driver's g and gn). A pass that holds x forms
+    // the gradient from it (k_commit UG, k_axpy_dot_x); every other reader has the buffer
+    // filled first (ug_in), and a write to either vector ends the entry (ug_out).
+    struct Ug {
+        double* g;  // nullptr: free
+        const double* x;
+        int obj, stored;
+    };
+    Ug ug[2];
+    int ug_on;      // entries are made: one rank, the launch sequence, no persistent two-loop
+    int ug_poison;  // LBFGS_STORE_G=poison: an unstored gradient's buffer is filled with NaN (tests)
 };
 
+#define LBK_UG_SLOT (LBK_NSLOTS - 4) /* scratch result slot of lbk_ug_materialise (no solver path uses it) */
+// fills the buffer of unstored gradient c->ug[i] (k_objective at its x; lbfgs_kernels.hip)
+extern "C" int lbk_ug_materialise(lbk_ctx* c, int i);
+
 namespace {
+
+// Unstored gradients, the entry points' side. ug_in: a vector about to be read as an input - if it
+// is an unstored gradient, it is stored first. ug_out: vectors about to be written - an entry whose
+// gradient buffer is among them ends; an unstored entry whose x is among them (its own buffer is
+// not) is stored first, then ends. Both come first in an entry point: they may launch.
+inline int ug_find(const lbk_ctx* c, const double* p) {
+    for (int i = 0; i < 2; ++i)
+        if (c->ug[i].g && c->ug[i].g == p) return i;
+    return -1;
+}
+inline int ug_in(lbk_ctx* c, const double* p) {
+    const int i = p ? ug_find(c, p) : -1;
+    return i >= 0 && !c->ug[i].stored ? lbk_ug_materialise(c, i) : 0;
+}
+inline int ug_out(lbk_ctx* c, std::initializer_list<const double*> w) {
+    for (auto& e : c->ug)
+        for (const double* p : w)
+            if (e.g && e.g == p) e.g = nullptr;
+    for (int i = 0; i < 2; ++i)
+        for (const double* p : w)
+            if (c->ug[i].g && c->ug[i].x == p) {
+                if (!c->ug[i].stored) {
+                    const int rc = lbk_ug_materialise(c, i);
+                    if (rc) return rc;
+                }
+                c->ug[i].g = nullptr;
+            }
+    return 0;
+}
+// Data from outside the passes enters a vector (an upload, a copy: every solver start begins with
+// one): every unstored gradient is stored and every entry ends, so that no entry outlives the
+// solve that made it - a later solve may write these buffers from outside the device layer (a
+// device-callback objective's gradient).
+inline int ug_flush(lbk_ctx* c) {
+    for (int i = 0; i < 2; ++i) {
+        if (c->ug[i].g && !c->ug[i].stored) {
+            const int rc = lbk_ug_materialise(c, i);
+            if (rc) return rc;
+        }
+        c->ug[i].g = nullptr;
+    }
+    return 0;
+}
+// after a pass that computed grad f(x) of a built-in objective for the buffer g (stored or not)
+inline void ug_record(lbk_ctx* c, double* g, const double* x, int obj, int stored) {
+    if (!c->ug_on || obj < 0 || obj > LBK_OBJ_QUAD_SEPARABLE) return;
+    int k = ug_find(c, g);
+    for (int i = 0; k < 0 && i < 2; ++i)
+        if (!c->ug[i].g) k = i;
+    if (k < 0) return;  // (no free entry: g is stored, or the caller stores it)
+    c->ug[k] = {g, x, obj, stored};
+}
 
 #define HIPCHK(c, expr)                                                                      \
     do {                                                                                     \

@@ -80,6 +80,7 @@ extern "C" {
 
 int lbk_vf_ghost_init(lbk_ctx* c, double* x, double* g, int wslot) {
     if (c->geo.world == 1) return 0;
+    if (const int rc_ = ug_in(c, g)) return rc_;
     return vf_exchange_ghosts(c, wslot, x, g, nullptr, nullptr);
 }
 
@@ -93,6 +94,9 @@ int lbk_vf_bucket(int h) {
 int lbk_vf_commit(lbk_ctx* c, int obj, int h, const double* x, const double* g, const double* const* S,
                   const double* const* Y, const double* cs, const double* cy, double cg, double alpha,
                   const double* cand, double* xn, double* gn, double* so, double* yo, int wslot, int* hb_out) {
+    // (vector-free contexts make no unstored gradients themselves: no TWOLOOP lbk_commit)
+    if (const int rc_ = ug_in(c, g)) return rc_;
+    if (const int rc_ = ug_out(c, {xn, gn, so, yo})) return rc_;
     const int hb = lbk_vf_bucket(h);
     if (hb < 0 || wslot < LBK_WSLOT0 || wslot >= LBK_WSLOT0 + LBK_NWSLOTS) {
         snprintf(c->err, sizeof c->err, "lbk_vf_commit: h=%d (max %d), slot %d", h, LBK_VF_HMAX, wslot);
@@ -110,6 +114,8 @@ int lbk_vf_commit(lbk_ctx* c, int obj, int h, const double* x, const double* g, 
 
 int lbk_vf_dir(lbk_ctx* c, int h, double* d, const double* g, const double* const* S, const double* const* Y,
                const double* cs, const double* cy, double cg) {
+    if (const int rc_ = ug_in(c, g)) return rc_;
+    if (const int rc_ = ug_out(c, {d})) return rc_;
     const int hb = lbk_vf_bucket(h);
     if (hb < 0) return -1;
     switch (hb) {
