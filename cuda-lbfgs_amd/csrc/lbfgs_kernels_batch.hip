@@ -3,7 +3,14 @@
 // limit and differ in x0, each solved by ONE workgroup that runs the whole loop of iterate()
 // (lbfgs_driver.c) on the device. A translation unit of its own: twelve large kernels for the stencil
 // objectives (k_batch_solve), and four for dense quadratics with each problem's own A and b
-// (k_batch_solve_dense, further down: the driver's external-objective path restated).
+// (k_batch_solve_dense, further down: the driver's external-objective path).
+//
+// The two kernel templates follow different branches of iterate() and stay two kernels. What the
+// branches have in common is written once, as force-inlined stages that both call (batch_enter,
+// batch_iter_top, batch_direction, batch_materialise_d, batch_search_begin, batch_accept,
+// batch_leave, with BatchView / BatchIter for the vectors), so the host's expressions in the host's
+// operand order are kept in one place; a kernel body is the sequence of its stages with only its
+// own evaluation, trial and commit inline.
 //
 // Every pass walks the problem's canonical segments one after another with the per-segment code of
 // the launch sequence (seg_at, stream, the Op* operators, wave_sum, ((w0 + w1) + (w2 + w3))), so
@@ -70,6 +77,12 @@ struct BatchLds {
     BatchWave wv[4];
 };
 
+__device__ __forceinline__ void batch_stage_sync() {  // stores of one stage before loads of the next
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
 // One pass of one problem: the segments in order, each exactly as its workgroup of the launch
 // sequence streams it; then the fixed-order total (coop_pass's nseg <= 64 form). The barrier with
 // its workgroup-scope fences also orders this pass's vector stores before the next pass's loads
@@ -95,9 +108,7 @@ __device__ __forceinline__ void batch_pass(const Op& op, const Geo& geo, BatchLd
             if (lane == 0) L.ws[w][k][sg] = v;
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    batch_stage_sync();
 #pragma unroll
     for (int k = w; k < K; k += 4) {  // wave w: components w, w + 4; lane j: segment j
         const double p = lane < nseg ? (L.ws[0][k][lane] + L.ws[1][k][lane]) + (L.ws[2][k][lane] + L.ws[3][k][lane]) : 0.0;
@@ -123,143 +134,279 @@ __device__ __forceinline__ void batch_commit(const Geo& geo, BatchLds& L, const 
                              geo, L, tot);
 }
 
+// ---------------------------------------------------------------------------------------
+// The stages of iterate() that k_batch_solve and k_batch_solve_dense share, each written once.
+// They take the wave's records by reference and keep nothing of them in locals across a pass.
+// ---------------------------------------------------------------------------------------
+
+// one problem's vectors (x g xn gn d q r, then the m + 1 pairs) and its trace rows
+struct BatchView {
+    double* vb;       // element 0 of vector 0
+    int64_t vstride;
+    double* trf;      // [3][tr_cap]: f, |g|, alpha; null without a trace
+    __device__ __forceinline__ double* vec(int i) const { return vb + (int64_t)i * vstride; }
+    __device__ __forceinline__ double* d() const { return vec(4); }
+    __device__ __forceinline__ double* q() const { return vec(5); }
+    __device__ __forceinline__ double* r() const { return vec(6); }
+    __device__ __forceinline__ double* s(int pair) const { return vec(7 + 2 * pair); }
+    __device__ __forceinline__ double* y(int pair) const { return vec(8 + 2 * pair); }
+};
+
+__device__ __forceinline__ BatchView batch_view(const BatchArgs& a, int p) {
+    return {a.base + (int64_t)p * a.pstride, a.vstride, a.trace ? a.tr + (int64_t)p * 3 * a.tr_cap : nullptr};
+}
+
+// one iteration's vectors: which of x/xn and g/gn is current, and the spare pair the commit fills
+struct BatchIter {
+    double *x, *xn, *g, *gn, *so, *yo;
+};
+
+// Entering a problem. A new solve starts a fresh record and moves x0 into the vector layout (the
+// kernel then evaluates there); a later launch loads the record. True when the problem finished in
+// an earlier launch (uniform).
+__device__ __forceinline__ bool batch_enter(const BatchArgs& a, const BatchView& V, int p, int64_t n, BatchState& S) {
+    if (!a.init) {
+        const BatchState* G = a.st + p;
+        if (G->status != LBFGS_STATUS_RUNNING) return true;
+        S = *G;
+        return false;
+    }
+    S = BatchState();
+    S.status = LBFGS_STATUS_RUNNING;
+    S.h_min = S.h_max = -1;
+    double* x0 = V.vec(0);
+    for (int64_t i = threadIdx.x; i < n; i += LB_BLOCK) x0[i] = a.xio[(int64_t)p * n + i];
+    batch_stage_sync();
+    return false;
+}
+
+__device__ __forceinline__ void batch_trace_push(const BatchArgs& a, const BatchView& V, BatchState& S, double f,
+                                                 double gn) {
+    if (!V.trf) return;
+    if (threadIdx.x == 0 && S.tr_len < a.tr_cap) {
+        V.trf[S.tr_len] = f;
+        V.trf[a.tr_cap + S.tr_len] = gn;
+        V.trf[2 * a.tr_cap + S.tr_len] = __builtin_nan("");
+    }
+    S.tr_len++;
+}
+
+// the accepted step into the entry that the iteration's top pushed
+__device__ __forceinline__ void batch_trace_step(const BatchArgs& a, const BatchView& V, const BatchState& S,
+                                                 double alpha) {
+    if (V.trf && threadIdx.x == 0 && S.tr_len - 1 < a.tr_cap) V.trf[2 * a.tr_cap + S.tr_len - 1] = alpha;
+}
+
+// Top of an iteration; true when it ends the problem (status set).
+__device__ __forceinline__ bool batch_iter_top(const BatchArgs& a, const BatchView& V, BatchState& S, BatchIter& I) {
+    if (S.k >= a.max_iterations) {  // lbfgs.cpp:201-202
+        batch_trace_push(a, V, S, S.f_cur, sqrt(S.gg));
+        S.status = LBFGS_STATUS_MAX_ITER;
+        return true;
+    }
+    const int h = S.h;
+    I.x = V.vec(S.flip ? 2 : 0);
+    I.xn = V.vec(S.flip ? 0 : 2);
+    I.g = V.vec(S.flip ? 3 : 1);
+    I.gn = V.vec(S.flip ? 1 : 3);
+    I.so = V.s(S.free_pair);
+    I.yo = V.y(S.free_pair);
+    const double gnorm = sqrt(S.gg);
+    batch_trace_push(a, V, S, S.f_cur, gnorm);
+    if (gnorm < a.tol) {  // :80-84
+        S.status = LBFGS_STATUS_CONVERGED;
+        return true;
+    }
+    if (S.h_min < 0 || h < S.h_min) S.h_min = h;
+    if (h > S.h_max) S.h_max = h;
+    return false;
+}
+
+// Search direction (:87-143): the validity tests and the two-loop's passes but the last update.
+// Leaves W.dmode, and for TWOLOOP W.coef, W.rho_top, W.top with r holding all but that update.
+__device__ __forceinline__ void batch_direction(const BatchView& V, const BatchIter& I, const Geo& geo, BatchLds& L,
+                                                BatchState& S, BatchWave& W) {
+    const int h = S.h;
+    double* const q = V.q();
+    double* const r = V.r();
+    W.dmode = LBK_D_NEG_G;
+    double gamma = 0.0;
+    if (!(S.k == 0 || h == 0)) {
+        int bad_rho = 0;
+        for (int i = h - 1; i >= 0; --i)
+            if (!isfinite(1.0 / S.sy[S.ring[i]])) bad_rho = 1;  // :102-108
+        if (bad_rho) {
+            S.ev[2]++;
+        } else {
+            const int top = S.ring[h - 1];
+            gamma = S.sy[top] / S.yy[top];  // :117-118
+            if (gamma <= 0 || !isfinite(gamma))
+                S.ev[3]++;
+            else
+                W.dmode = LBK_D_TWOLOOP;
+        }
+    }
+    if (W.dmode != LBK_D_TWOLOOP) return;
+    const int top = S.ring[h - 1];
+    const double rho_top = 1.0 / S.sy[top];
+    double t1[1];
+    // alpha_{h-1} = rho_{h-1} (s_{h-1} . g): the previous commit's s . g_new, or a dot pass
+    if (S.sg_valid) {
+        t1[0] = S.sg;
+    } else {
+        batch_pass<1>(OpDot<false>{V.s(top), I.g}, geo, L, t1);
+        S.vecs += 2.0;
+    }
+    W.TA[h - 1] = t1[0];
+    double alpha = rho_top * t1[0];
+    const double* qsrc = I.g;
+    for (int i = h - 2; i >= 0; --i) {  // q = q - alpha_{i+1} y_{i+1};  s_i . q
+        batch_pass<1>(OpAxpyDot<false>{q, qsrc, V.y(S.ring[i + 1]), V.s(S.ring[i]), alpha}, geo, L, t1);
+        S.vecs += 4.0;
+        W.TA[i] = t1[0];
+        alpha = (1.0 / S.sy[S.ring[i]]) * t1[0];
+        qsrc = q;
+    }
+    batch_pass<1>(OpMid<false>{r, qsrc, V.y(S.ring[0]), alpha, gamma}, geo, L, t1);
+    S.vecs += 3.0;
+    for (int i = 0; i + 1 < h; ++i) {  // r += s_i (alpha_i - beta_i);  y_{i+1} . r
+        const double rho = 1.0 / S.sy[S.ring[i]];
+        const double beta = rho * t1[0];
+        const double alph = rho * W.TA[i];
+        batch_pass<1>(OpAxpy2Dot<false>{r, r, V.s(S.ring[i]), V.y(S.ring[i + 1]), alph - beta}, geo, L, t1);
+        S.vecs += 4.0;
+    }
+    // the last second-loop update rides the commit (k_commit TWOLOOP) or the pass that materialises d
+    const double beta = rho_top * t1[0];
+    const double alph = rho_top * W.TA[h - 1];
+    W.coef = alph - beta;
+    W.rho_top = rho_top;
+    W.top = top;
+}
+
+// d into its buffer (materialize_d: k_last / k_negdot); the pass total is g . d
+__device__ __forceinline__ double batch_materialise_d(const BatchView& V, const BatchIter& I, const Geo& geo,
+                                                      BatchLds& L, BatchState& S, BatchWave& W) {
+    double t1[1];
+    if (W.dmode == LBK_D_TWOLOOP) {
+        batch_pass<1>(OpLast<false>{V.d(), V.r(), V.s(W.top), I.g, W.coef}, geo, L, t1);
+        S.vecs += 4.0;
+    } else {
+        batch_pass<1>(OpNegDot<false>{V.d(), I.g}, geo, L, t1);
+        S.vecs += 2.0;
+    }
+    return t1[0];
+}
+
+// the direction read from d's buffer (k_commit's / k_trials' BUF)
+__device__ __forceinline__ DirArgs batch_buf_args(const BatchView& V, const BatchIter& I) {
+    DirArgs db = {};
+    db.dsrc = V.d();
+    db.g = I.g;
+    db.g_hi = LBK_GROUPS;
+    return db;
+}
+
+// The line search (:156) from the top: everything but the fused path's caches.
+__device__ __forceinline__ void batch_search_begin(const BatchArgs& a, const BatchState& S, lbk_search& s, double gd) {
+    __builtin_memset(&s, 0, sizeof s);
+    s.f_x = S.f_cur;
+    s.gd = gd;
+    s.c1 = a.K.c1;
+    s.c2 = a.K.c2;
+    s.amin = a.K.wolfe_interp_min;
+    s.init = a.K.initial_step;
+    s.beta = a.K.backtracking_alpha;
+    s.tol = a.K.backtracking_tol;
+    s.alpha = a.K.initial_step;
+    s.alpha_hi = INFINITY;
+    s.f_lo = s.f_prev = S.f_cur;
+    s.dphi_lo = gd;
+}
+
+// Accepting the step (:182-198) from the commit's totals: the pair stored when s . y > 0, the ring
+// rotated with the spare pair once it is full; x = x_new, g = g_new.
+__device__ __forceinline__ void batch_accept(int m, BatchState& S, const BatchWave& W) {
+    const int h = S.h;
+    const double sy = W.tot[LBK_C_SY];
+    if (sy > 0) {  // :182-191
+        const int pair = S.free_pair;
+        if (h >= m) {
+            const int oldest = S.ring[0];
+            for (int i = 0; i + 1 < m; ++i) S.ring[i] = S.ring[i + 1];
+            S.ring[m - 1] = pair;
+            S.free_pair = oldest;
+        } else {
+            S.ring[h] = pair;
+            S.h = h + 1;
+            S.free_pair = h + 1;  // pool slots 0..h used, h + 1 is free
+        }
+        S.sy[pair] = sy;
+        S.yy[pair] = W.tot[LBK_C_YY];
+        S.sg_valid = 1;
+        S.sg = W.tot[LBK_C_SG];
+    } else {  // :192-195
+        S.ev[1]++;
+        S.sg_valid = 0;
+    }
+    S.flip ^= 1;  // :197-198
+    S.gg = W.tot[LBK_C_GG];
+    S.k++;
+}
+
+// Leaving a problem: x out when it finished in this launch, the record stored, the running flag.
+__device__ __forceinline__ void batch_leave(const BatchArgs& a, const BatchView& V, int p, int64_t n,
+                                            const BatchState& S) {
+    if (S.status != LBFGS_STATUS_RUNNING) {
+        const double* xc = V.vec(S.flip ? 2 : 0);
+        for (int64_t i = threadIdx.x; i < n; i += LB_BLOCK) a.xio[(int64_t)p * n + i] = xc[i];
+    }
+    if (threadIdx.x == 0) {
+        a.st[p] = S;
+        if (S.status == LBFGS_STATUS_RUNNING) atomicOr(a.running, 1);
+    }
+}
+
+// The fused stencil branch of iterate(): the first trial at initial_step rides the commit, the
+// search starts from that pass's totals, and the commit is repeated only at another step.
 template <int OBJ, int LS>
 __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) {
     __shared__ BatchLds L;
     constexpr bool FG = LS == 2 || LS == 3;
     constexpr bool CAND = LS == 0;  // the backtracking search's second step rides the first commit
     constexpr int NC = LBK_TRIALS_NC;
-    const int t = threadIdx.x, m = a.m;
     const int64_t n = geo.n;
-    BatchWave& W = L.wv[t >> 6];
+    BatchWave& W = L.wv[threadIdx.x >> 6];
     BatchState& S = W.st;
     lbk_search& s = W.s;
     for (int p = blockIdx.x; p < a.B; p += gridDim.x) {
-        BatchState* G = a.st + p;
-        double* vb = a.base + (int64_t)p * a.pstride;
-        auto vec = [&](int i) { return vb + (int64_t)i * a.vstride; };
-        double* const d = vec(4);
-        double* const q = vec(5);
-        double* const r = vec(6);
-        if (a.init) {  // a new solve: x = x0, then f and g.g at x0 (lbfgs.cpp:29-30)
-            S = BatchState();
-            S.status = LBFGS_STATUS_RUNNING;
-            S.h_min = S.h_max = -1;
-            double* x0 = vec(0);
-            for (int64_t i = t; i < n; i += LB_BLOCK) x0[i] = a.xio[(int64_t)p * n + i];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __syncthreads();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        const BatchView V = batch_view(a, p);
+        if (batch_enter(a, V, p, n, S)) continue;
+        if (a.init) {  // f and g.g at x0 (lbfgs.cpp:29-30)
             DirArgs da0 = {};
             double t2[2];
-            batch_pass<2>(OpObjective<OBJ, true, true, false>{x0, da0, 0.0, vec(1), n, n}, geo, L, t2);
+            batch_pass<2>(OpObjective<OBJ, true, true, false>{V.vec(0), da0, 0.0, V.vec(1), n, n}, geo, L, t2);
             S.f_cur = t2[0];
             S.gg = t2[1];
             S.vecs = 2.0;
-        } else {
-            if (G->status != LBFGS_STATUS_RUNNING) continue;  // uniform: finished in an earlier launch
-            S = *G;
         }
-        double* trf = a.trace ? a.tr + (int64_t)p * 3 * a.tr_cap : nullptr;
-        auto trace_push = [&](double f, double gn) {
-            if (!trf) return;
-            if (t == 0 && S.tr_len < a.tr_cap) {
-                trf[S.tr_len] = f;
-                trf[a.tr_cap + S.tr_len] = gn;
-                trf[2 * a.tr_cap + S.tr_len] = __builtin_nan("");
-            }
-            S.tr_len++;
-        };
 
         for (int it = 0; it < a.iters; ++it) {
-            if (S.k >= a.max_iterations) {  // lbfgs.cpp:201-202
-                trace_push(S.f_cur, sqrt(S.gg));
-                S.status = LBFGS_STATUS_MAX_ITER;
-                break;
-            }
-            const int h = S.h;
-            double* const x = vec(S.flip ? 2 : 0);
-            double* const xn = vec(S.flip ? 0 : 2);
-            double* const g = vec(S.flip ? 3 : 1);
-            double* const gn = vec(S.flip ? 1 : 3);
-            double* const so = vec(7 + 2 * S.free_pair);
-            double* const yo = vec(8 + 2 * S.free_pair);
-            const double gnorm = sqrt(S.gg);
-            trace_push(S.f_cur, gnorm);
-            if (gnorm < a.tol) {  // :80-84
-                S.status = LBFGS_STATUS_CONVERGED;
-                break;
-            }
-            if (S.h_min < 0 || h < S.h_min) S.h_min = h;
-            if (h > S.h_max) S.h_max = h;
+            BatchIter I;
+            if (batch_iter_top(a, V, S, I)) break;
+            batch_direction(V, I, geo, L, S, W);
 
-            // ---- search direction (:87-143) and the fused first trial at a0 with the commit ----
+            // ---- the fused first trial at a0 with the commit ----
             const double a0 = a.K.initial_step;
             const double cand = CAND ? a0 * a.K.backtracking_alpha : 0.0;
-            W.dmode = LBK_D_NEG_G;
-            double gamma = 0.0;
-            if (!(S.k == 0 || h == 0)) {
-                int bad_rho = 0;
-                for (int i = h - 1; i >= 0; --i)
-                    if (!isfinite(1.0 / S.sy[S.ring[i]])) bad_rho = 1;  // :102-108
-                if (bad_rho) {
-                    S.ev[2]++;
-                } else {
-                    const int top = S.ring[h - 1];
-                    gamma = S.sy[top] / S.yy[top];  // :117-118
-                    if (gamma <= 0 || !isfinite(gamma))
-                        S.ev[3]++;
-                    else
-                        W.dmode = LBK_D_TWOLOOP;
-                }
-            }
-            if (W.dmode == LBK_D_TWOLOOP) {
-                const int top = S.ring[h - 1];
-                const double rho_top = 1.0 / S.sy[top];
-                double t1[1];
-                // alpha_{h-1} = rho_{h-1} (s_{h-1} . g): the previous commit's s . g_new, or a dot pass
-                if (S.sg_valid) {
-                    t1[0] = S.sg;
-                } else {
-                    batch_pass<1>(OpDot<false>{vec(7 + 2 * top), g}, geo, L, t1);
-                    S.vecs += 2.0;
-                }
-                W.TA[h - 1] = t1[0];
-                double alpha = rho_top * t1[0];
-                const double* qsrc = g;
-                for (int i = h - 2; i >= 0; --i) {  // q = q - alpha_{i+1} y_{i+1};  s_i . q
-                    batch_pass<1>(OpAxpyDot<false>{q, qsrc, vec(8 + 2 * S.ring[i + 1]), vec(7 + 2 * S.ring[i]), alpha},
-                                  geo, L, t1);
-                    S.vecs += 4.0;
-                    W.TA[i] = t1[0];
-                    alpha = (1.0 / S.sy[S.ring[i]]) * t1[0];
-                    qsrc = q;
-                }
-                batch_pass<1>(OpMid<false>{r, qsrc, vec(8 + 2 * S.ring[0]), alpha, gamma}, geo, L, t1);
-                S.vecs += 3.0;
-                for (int i = 0; i + 1 < h; ++i) {  // r += s_i (alpha_i - beta_i);  y_{i+1} . r
-                    const double rho = 1.0 / S.sy[S.ring[i]];
-                    const double beta = rho * t1[0];
-                    const double alph = rho * W.TA[i];
-                    batch_pass<1>(OpAxpy2Dot<false>{r, r, vec(7 + 2 * S.ring[i]), vec(8 + 2 * S.ring[i + 1]), alph - beta},
-                                  geo, L, t1);
-                    S.vecs += 4.0;
-                }
-                // the last second-loop update rides the commit (k_commit TWOLOOP)
-                const double beta = rho_top * t1[0];
-                const double alph = rho_top * W.TA[h - 1];
-                W.coef = alph - beta;
-                W.rho_top = rho_top;
-                W.top = top;
-            }
             // how the direction is formed until d is materialised (k_commit's TWOLOOP / NEG_G)
             auto dir_args = [&]() {
                 DirArgs dd = {};
-                dd.g = g;
+                dd.g = I.g;
                 dd.g_hi = LBK_GROUPS;
                 if (W.dmode == LBK_D_TWOLOOP) {
-                    dd.dsrc = r;
-                    dd.s = vec(7 + 2 * W.top);
+                    dd.dsrc = V.r();
+                    dd.s = V.s(W.top);
                     dd.coef = W.coef;
                     dd.rho = W.rho_top;
                 }
@@ -269,10 +416,10 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) 
             for (bool fell_back = false;;) {  // the first trial at a0 and the commit, in one pass
                 const DirArgs dd = dir_args();
                 if (W.dmode == LBK_D_TWOLOOP) {
-                    batch_commit<OBJ, LBK_D_TWOLOOP, CAND>(geo, L, x, dd, a0, xn, gn, so, yo, cand, W.tot);
+                    batch_commit<OBJ, LBK_D_TWOLOOP, CAND>(geo, L, I.x, dd, a0, I.xn, I.gn, I.so, I.yo, cand, W.tot);
                     S.vecs += 8.0;
                 } else {
-                    batch_commit<OBJ, LBK_D_NEG_G, CAND>(geo, L, x, dd, a0, xn, gn, so, yo, cand, W.tot);
+                    batch_commit<OBJ, LBK_D_NEG_G, CAND>(geo, L, I.x, dd, a0, I.xn, I.gn, I.so, I.yo, cand, W.tot);
                     S.vecs += 6.0;
                 }
                 S.commits++;
@@ -283,16 +430,8 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) 
                 fell_back = true;
             }
 
-            // ---- the line search (:156), from the top, with the host's caches ----
-            __builtin_memset(&s, 0, sizeof s);
-            s.f_x = S.f_cur;
-            s.gd = gd;
-            s.c1 = a.K.c1;
-            s.c2 = a.K.c2;
-            s.amin = a.K.wolfe_interp_min;
-            s.init = a.K.initial_step;
-            s.beta = a.K.backtracking_alpha;
-            s.tol = a.K.backtracking_tol;
+            // ---- the line search, with the host's caches of that pass ----
+            batch_search_begin(a, S, s, gd);
             s.have_spec = 1;
             s.spec_a = a0;
             s.spec_f = W.tot[LBK_C_F];
@@ -302,30 +441,14 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) 
                 s.cand_a = cand;
                 s.cand_f = W.tot[LBK_C_FC];
             }
-            s.alpha = a.K.initial_step;
-            s.alpha_hi = INFINITY;
-            s.f_lo = s.f_prev = S.f_cur;
-            s.dphi_lo = gd;
             W.d_ready = W.capped = W.passes = 0;
-            // d into its buffer before the first pass that reads it (materialize_d: k_last / k_negdot)
-            auto need_d = [&]() {
+            // d into its buffer before the first pass that reads it. Always inlined: left to the cost
+            // model it is a call in some of the twelve kernels, and what it captures (geo, the view,
+            // the iteration's vectors) then lives in scratch
+            auto need_d = [&]() __attribute__((always_inline)) {
                 if (W.d_ready) return;
-                double t1[1];
-                if (W.dmode == LBK_D_TWOLOOP) {
-                    batch_pass<1>(OpLast<false>{d, r, vec(7 + 2 * W.top), g, W.coef}, geo, L, t1);
-                    S.vecs += 4.0;
-                } else {
-                    batch_pass<1>(OpNegDot<false>{d, g}, geo, L, t1);
-                    S.vecs += 2.0;
-                }
+                batch_materialise_d(V, I, geo, L, S, W);
                 W.d_ready = 1;
-            };
-            auto buf_args = [&]() {
-                DirArgs db = {};
-                db.dsrc = d;
-                db.g = g;
-                db.g_hi = LBK_GROUPS;
-                return db;
             };
             auto trial = [&](double alpha, bool need_g, double& f, double& dphi) -> bool {
                 if (search_cached(s, alpha, need_g, f, dphi)) return true;
@@ -337,14 +460,14 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) 
                 W.passes++;
                 S.vecs += 2.0;
                 if (FG) {
-                    OpTrials<OBJ, LBK_D_BUF, 1, true, false> op{x, buf_args(), {alpha}, n, n};
+                    OpTrials<OBJ, LBK_D_BUF, 1, true, false> op{I.x, batch_buf_args(V, I), {alpha}, n, n};
                     double tt[2];
                     batch_pass<2>(op, geo, L, tt);
                     search_note_fg(s, alpha, tt);
                     f = tt[0];
                     dphi = tt[1];
                 } else {
-                    OpTrials<OBJ, LBK_D_BUF, NC, false, false> op{x, buf_args(), {}, n, n};
+                    OpTrials<OBJ, LBK_D_BUF, NC, false, false> op{I.x, batch_buf_args(V, I), {}, n, n};
                     search_chain<LS>(s, alpha, op.a);
                     double tt[NC];
                     batch_pass<NC>(op, geo, L, tt);
@@ -361,12 +484,13 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) 
                 break;
             }
             const double alpha = s.step;
-            if (trf && t == 0 && S.tr_len - 1 < a.tr_cap) trf[2 * a.tr_cap + S.tr_len - 1] = alpha;
+            batch_trace_step(a, V, S, alpha);
 
             // ---- commit (:159-198): again at the search's step when that is not the first trial's ----
             if (!(alpha == a0)) {
                 need_d();
-                batch_commit<OBJ, LBK_D_BUF, false>(geo, L, x, buf_args(), alpha, xn, gn, so, yo, 0.0, W.tot);
+                batch_commit<OBJ, LBK_D_BUF, false>(geo, L, I.x, batch_buf_args(V, I), alpha, I.xn, I.gn, I.so, I.yo, 0.0,
+                                                    W.tot);
                 S.vecs += 7.0;
                 S.commits++;
             }
@@ -375,50 +499,20 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) 
                 S.status = LBFGS_STATUS_LS_FAILED;
                 break;
             }
-            const double sy = W.tot[LBK_C_SY];
-            if (sy > 0) {  // :182-191
-                const int pair = S.free_pair;
-                if (h >= m) {
-                    const int oldest = S.ring[0];
-                    for (int i = 0; i + 1 < m; ++i) S.ring[i] = S.ring[i + 1];
-                    S.ring[m - 1] = pair;
-                    S.free_pair = oldest;
-                } else {
-                    S.ring[h] = pair;
-                    S.h = h + 1;
-                    S.free_pair = h + 1;  // pool slots 0..h used, h + 1 is free
-                }
-                S.sy[pair] = sy;
-                S.yy[pair] = W.tot[LBK_C_YY];
-                S.sg_valid = 1;
-                S.sg = W.tot[LBK_C_SG];
-            } else {  // :192-195
-                S.ev[1]++;
-                S.sg_valid = 0;
-            }
-            S.flip ^= 1;  // x = x_new, g = g_new (:197-198)
-            S.gg = W.tot[LBK_C_GG];
-            S.k++;
+            batch_accept(a.m, S, W);
         }
-
-        if (S.status != LBFGS_STATUS_RUNNING) {  // finished in this launch: x out
-            const double* xc = vec(S.flip ? 2 : 0);
-            for (int64_t i = t; i < n; i += LB_BLOCK) a.xio[(int64_t)p * n + i] = xc[i];
-        }
-        if (t == 0) {
-            *G = S;
-            if (S.status == LBFGS_STATUS_RUNNING) atomicOr(a.running, 1);
-        }
+        batch_leave(a, V, p, n, S);
     }
 }
 
 // ---------------------------------------------------------------------------------------
 // Dense quadratics, every problem with its own A and b (lbfgs_batch_set_dense_quadratics):
-// k_batch_solve_dense restates the external-objective branch of iterate() (lbfgs_driver.c,
-// ext_obj()), not the fused stencil branch above. d is materialised before the search (k_last /
-// k_negdot, whose total is g . d), the search starts with nothing cached, a trial is z = x + alpha d
-// (k_point), the rows of A z (k_dense_rows) and the terms pass (k_terms_dot), the commit reads the
-// gradient it is given (OpCommit<LBK_OBJ_NONE>) and takes f from the evaluation.
+// k_batch_solve_dense follows the external-objective branch of iterate() (lbfgs_driver.c,
+// ext_obj()), not the fused stencil branch above, over the same stages. d is materialised before
+// the search (k_last / k_negdot, whose total is g . d), the search starts with nothing cached, a
+// trial is z = x + alpha d (k_point), the rows of A z (k_dense_rows) and the terms pass
+// (k_terms_dot), the commit reads the gradient it is given (OpCommit<LBK_OBJ_NONE>) and takes f
+// from the evaluation.
 // ---------------------------------------------------------------------------------------
 struct BatchDenseArgs {
     const double* A;   // [B][n][n], or one [n][n] when astride is 0
@@ -438,12 +532,6 @@ struct BatchDenseLds {
     BatchLds L;
     DenseWave dw[4];
 };
-
-__device__ __forceinline__ void batch_stage_sync() {  // stores of one stage before loads of the next
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // z = x + alpha d, k_point's arithmetic. k_point also forms the two ghost cells, 0 + alpha * 0; no
 // stage of the dense path reads them, and a step that is not finite would leave NaN there for a
@@ -483,19 +571,15 @@ template <int LS>
 __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, BatchDenseArgs dq, Geo geo) {
     __shared__ BatchDenseLds LD;
     BatchLds& L = LD.L;
-    const int t = threadIdx.x, m = a.m;
+    const int t = threadIdx.x;
     const int64_t n = geo.n;
     BatchWave& W = L.wv[t >> 6];
     DenseWave& D = LD.dw[t >> 6];
     BatchState& S = W.st;
     lbk_search& s = W.s;
     for (int p = blockIdx.x; p < a.B; p += gridDim.x) {
-        BatchState* G = a.st + p;
-        double* vb = a.base + (int64_t)p * a.pstride;
-        auto vec = [&](int i) { return vb + (int64_t)i * a.vstride; };
-        double* const d = vec(4);
-        double* const q = vec(5);
-        double* const r = vec(6);
+        const BatchView V = batch_view(a, p);
+        double* const d = V.d();
         const double* const Ap = dq.A + (int64_t)p * dq.astride;
         const double* const bp = dq.b + (int64_t)p * n;
         double* const tv = dq.xbase + (int64_t)p * 2 * a.vstride;
@@ -506,123 +590,24 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, Bat
             batch_pass<2>(OpTermsDot<false>{tv, gout}, geo, L, t2);
             S.vecs += (double)n + 5.0;
         };
-        if (a.init) {  // a new solve: x = x0, then f, g and g.g at x0
-            S = BatchState();
-            S.status = LBFGS_STATUS_RUNNING;
-            S.h_min = S.h_max = -1;
-            double* x0 = vec(0);
-            for (int64_t i = t; i < n; i += LB_BLOCK) x0[i] = a.xio[(int64_t)p * n + i];
-            batch_stage_sync();
+        if (batch_enter(a, V, p, n, S)) continue;
+        if (a.init) {  // f, g and g.g at x0
             double t2[2];
-            eval(x0, vec(1), t2);
+            eval(V.vec(0), V.vec(1), t2);
             S.f_cur = t2[0];
             S.gg = t2[1];
-        } else {
-            if (G->status != LBFGS_STATUS_RUNNING) continue;  // uniform: finished in an earlier launch
-            S = *G;
         }
-        double* trf = a.trace ? a.tr + (int64_t)p * 3 * a.tr_cap : nullptr;
-        auto trace_push = [&](double f, double gn) {
-            if (!trf) return;
-            if (t == 0 && S.tr_len < a.tr_cap) {
-                trf[S.tr_len] = f;
-                trf[a.tr_cap + S.tr_len] = gn;
-                trf[2 * a.tr_cap + S.tr_len] = __builtin_nan("");
-            }
-            S.tr_len++;
-        };
 
         for (int it = 0; it < a.iters; ++it) {
-            if (S.k >= a.max_iterations) {
-                trace_push(S.f_cur, sqrt(S.gg));
-                S.status = LBFGS_STATUS_MAX_ITER;
-                break;
-            }
-            const int h = S.h;
-            double* const x = vec(S.flip ? 2 : 0);
-            double* const xn = vec(S.flip ? 0 : 2);
-            double* const g = vec(S.flip ? 3 : 1);
-            double* const gn = vec(S.flip ? 1 : 3);
-            double* const so = vec(7 + 2 * S.free_pair);
-            double* const yo = vec(8 + 2 * S.free_pair);
-            const double gnorm = sqrt(S.gg);
-            trace_push(S.f_cur, gnorm);
-            if (gnorm < a.tol) {
-                S.status = LBFGS_STATUS_CONVERGED;
-                break;
-            }
-            if (S.h_min < 0 || h < S.h_min) S.h_min = h;
-            if (h > S.h_max) S.h_max = h;
+            BatchIter I;
+            if (batch_iter_top(a, V, S, I)) break;
+            batch_direction(V, I, geo, L, S, W);
 
-            // ---- search direction: the two-loop's passes as in k_batch_solve ----
-            W.dmode = LBK_D_NEG_G;
-            double gamma = 0.0;
-            if (!(S.k == 0 || h == 0)) {
-                int bad_rho = 0;
-                for (int i = h - 1; i >= 0; --i)
-                    if (!isfinite(1.0 / S.sy[S.ring[i]])) bad_rho = 1;
-                if (bad_rho) {
-                    S.ev[2]++;
-                } else {
-                    const int top = S.ring[h - 1];
-                    gamma = S.sy[top] / S.yy[top];
-                    if (gamma <= 0 || !isfinite(gamma))
-                        S.ev[3]++;
-                    else
-                        W.dmode = LBK_D_TWOLOOP;
-                }
-            }
-            if (W.dmode == LBK_D_TWOLOOP) {
-                const int top = S.ring[h - 1];
-                const double rho_top = 1.0 / S.sy[top];
-                double t1[1];
-                if (S.sg_valid) {  // the previous commit's s . g_new
-                    t1[0] = S.sg;
-                } else {
-                    batch_pass<1>(OpDot<false>{vec(7 + 2 * top), g}, geo, L, t1);
-                    S.vecs += 2.0;
-                }
-                W.TA[h - 1] = t1[0];
-                double alpha = rho_top * t1[0];
-                const double* qsrc = g;
-                for (int i = h - 2; i >= 0; --i) {
-                    batch_pass<1>(OpAxpyDot<false>{q, qsrc, vec(8 + 2 * S.ring[i + 1]), vec(7 + 2 * S.ring[i]), alpha},
-                                  geo, L, t1);
-                    S.vecs += 4.0;
-                    W.TA[i] = t1[0];
-                    alpha = (1.0 / S.sy[S.ring[i]]) * t1[0];
-                    qsrc = q;
-                }
-                batch_pass<1>(OpMid<false>{r, qsrc, vec(8 + 2 * S.ring[0]), alpha, gamma}, geo, L, t1);
-                S.vecs += 3.0;
-                for (int i = 0; i + 1 < h; ++i) {
-                    const double rho = 1.0 / S.sy[S.ring[i]];
-                    const double beta = rho * t1[0];
-                    const double alph = rho * W.TA[i];
-                    batch_pass<1>(OpAxpy2Dot<false>{r, r, vec(7 + 2 * S.ring[i]), vec(8 + 2 * S.ring[i + 1]), alph - beta},
-                                  geo, L, t1);
-                    S.vecs += 4.0;
-                }
-                const double beta = rho_top * t1[0];
-                const double alph = rho_top * W.TA[h - 1];
-                W.coef = alph - beta;
-                W.rho_top = rho_top;
-                W.top = top;
-            }
-
-            // ---- d into its buffer (materialize_d: k_last / k_negdot), g . d that pass's total; a
-            // direction that is no descent direction gives way to -g, materialised again (once) ----
+            // ---- d into its buffer, g . d that pass's total; a direction that is no descent
+            // direction gives way to -g, materialised again (once) ----
             double gd;
             for (bool fell_back = false;;) {
-                double t1[1];
-                if (W.dmode == LBK_D_TWOLOOP) {
-                    batch_pass<1>(OpLast<false>{d, r, vec(7 + 2 * W.top), g, W.coef}, geo, L, t1);
-                    S.vecs += 4.0;
-                } else {
-                    batch_pass<1>(OpNegDot<false>{d, g}, geo, L, t1);
-                    S.vecs += 2.0;
-                }
-                gd = t1[0];
+                gd = batch_materialise_d(V, I, geo, L, S, W);
                 if (!(gd >= 0) || fell_back) break;
                 S.ev[0]++;
                 W.dmode = LBK_D_NEG_G;
@@ -632,7 +617,7 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, Bat
 
             auto point = [&](double alpha) {  // host_point_issue
                 if (D.hz_valid && D.hz_alpha == alpha) return;
-                dense_point(xn, x, d, alpha, n);
+                dense_point(I.xn, I.x, d, alpha, n);
                 S.vecs += 3.0;
                 D.hz_valid = 1;
                 D.hz_alpha = alpha;
@@ -643,7 +628,7 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, Bat
             auto eval_at = [&](double alpha, double* dst) {
                 point(alpha);
                 double t2[2];
-                eval(xn, dst, t2);
+                eval(I.xn, dst, t2);
                 D.hf_valid = 1;
                 D.hf_alpha = alpha;
                 D.hf_val = t2[0];
@@ -671,19 +656,7 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, Bat
             };
 
             // ---- the line search, from the top, nothing cached (no first trial rode a commit) ----
-            __builtin_memset(&s, 0, sizeof s);
-            s.f_x = S.f_cur;
-            s.gd = gd;
-            s.c1 = a.K.c1;
-            s.c2 = a.K.c2;
-            s.amin = a.K.wolfe_interp_min;
-            s.init = a.K.initial_step;
-            s.beta = a.K.backtracking_alpha;
-            s.tol = a.K.backtracking_tol;
-            s.alpha = a.K.initial_step;
-            s.alpha_hi = INFINITY;
-            s.f_lo = s.f_prev = S.f_cur;
-            s.dphi_lo = gd;
+            batch_search_begin(a, S, s, gd);
             W.capped = W.passes = 0;
             // lbfgs_driver.c trial() for an external objective: one step per call, f from its cache or
             // an evaluation, with need_g the gradient in gt and gt . d; the backtracking-Wolfe search
@@ -721,7 +694,7 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, Bat
                 break;
             }
             const double alpha = s.step;
-            if (trf && t == 0 && S.tr_len - 1 < a.tr_cap) trf[2 * a.tr_cap + S.tr_len - 1] = alpha;
+            batch_trace_step(a, V, S, alpha);
 
             // ---- commit (lbfgs_driver.c commit(), ext_obj): f at the step, then - unless the step
             // failed - the gradient at the step into gn, and the commit pass that reads it ----
@@ -731,52 +704,16 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, Bat
                 S.status = LBFGS_STATUS_LS_FAILED;
                 break;
             }
-            g_at(alpha, gn);
-            {
-                DirArgs db = {};
-                db.dsrc = d;
-                db.g = g;
-                db.g_hi = LBK_GROUPS;
-                batch_pass<7>(OpCommit<LBK_OBJ_NONE, LBK_D_BUF, false, false>{x, db, alpha, xn, gn, so, yo, n, n, 0.0},
-                              geo, L, W.tot);
-            }
+            g_at(alpha, I.gn);
+            batch_pass<7>(OpCommit<LBK_OBJ_NONE, LBK_D_BUF, false, false>{I.x, batch_buf_args(V, I), alpha, I.xn, I.gn,
+                                                                          I.so, I.yo, n, n, 0.0},
+                          geo, L, W.tot);
             W.tot[LBK_C_F] = f_new;
             S.vecs += 7.0;
             S.commits++;
-            const double sy = W.tot[LBK_C_SY];
-            if (sy > 0) {
-                const int pair = S.free_pair;
-                if (h >= m) {
-                    const int oldest = S.ring[0];
-                    for (int i = 0; i + 1 < m; ++i) S.ring[i] = S.ring[i + 1];
-                    S.ring[m - 1] = pair;
-                    S.free_pair = oldest;
-                } else {
-                    S.ring[h] = pair;
-                    S.h = h + 1;
-                    S.free_pair = h + 1;
-                }
-                S.sy[pair] = sy;
-                S.yy[pair] = W.tot[LBK_C_YY];
-                S.sg_valid = 1;
-                S.sg = W.tot[LBK_C_SG];
-            } else {
-                S.ev[1]++;
-                S.sg_valid = 0;
-            }
-            S.flip ^= 1;
-            S.gg = W.tot[LBK_C_GG];
-            S.k++;
+            batch_accept(a.m, S, W);
         }
-
-        if (S.status != LBFGS_STATUS_RUNNING) {  // finished in this launch: x out
-            const double* xc = vec(S.flip ? 2 : 0);
-            for (int64_t i = t; i < n; i += LB_BLOCK) a.xio[(int64_t)p * n + i] = xc[i];
-        }
-        if (t == 0) {
-            *G = S;
-            if (S.status == LBFGS_STATUS_RUNNING) atomicOr(a.running, 1);
-        }
+        batch_leave(a, V, p, n, S);
     }
 }
 
@@ -1029,8 +966,6 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
         a.K = *k;
     else
         lbfgs_constants_default(&a.K);
-    const batch_kernel_t kern = dense ? nullptr : batch_kernel(objective, line_search);
-    const batch_dense_kernel_t dkern = dense ? batch_dense_kernel(line_search) : nullptr;
     BatchDenseArgs dq;
     memset(&dq, 0, sizeof dq);
     if (dense) {
@@ -1039,16 +974,20 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
         dq.xbase = b->dq_x + LBK_FRONT;
         dq.astride = b->dq_shared ? 0 : b->n * b->n;
     }
+    // the one kernel of this solve and its arguments
+    const void* const kern = dense ? (const void*)batch_dense_kernel(line_search)
+                                   : (const void*)batch_kernel(objective, line_search);
+    void* args_stencil[] = {&a, &b->geo};
+    void* args_dense[] = {&a, &dq, &b->geo};
+    void** const kargs = dense ? args_dense : args_stencil;
     int grid = b->max_wg;
     if (grid <= 0) {  // every workgroup resident: occupancy x CUs
         int per_cu = 0;
-        if (dense)
-            BHIP(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dkern, LB_BLOCK, 0));
-        else
-            BHIP(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, LB_BLOCK, 0));
+        BHIP(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, LB_BLOCK, 0));
         grid = std::max(1, per_cu) * std::max(1, b->cus);
     }
     grid = std::min(grid, b->B);
+    auto launch = [&] { return hipLaunchKernel(kern, dim3(grid), dim3(LB_BLOCK), kargs, 0, b->stream); };
     // x0 up (one contiguous copy; each workgroup moves its problem's x0 into the vector layout)
     BHIP(b, hipMemcpyAsync(b->xio, x0_host, sizeof(double) * (size_t)b->n * (size_t)b->B, hipMemcpyHostToDevice,
                            b->stream));
@@ -1058,11 +997,7 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
     for (;;) {
         int running = 0;
         BHIP(b, hipMemsetAsync(b->running, 0, sizeof(int), b->stream));
-        if (dense)
-            hipLaunchKernelGGL(dkern, dim3(grid), dim3(LB_BLOCK), 0, b->stream, a, dq, b->geo);
-        else
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(LB_BLOCK), 0, b->stream, a, b->geo);
-        BHIP(b, hipGetLastError());
+        BHIP(b, launch());
         BHIP(b, hipMemcpyAsync(&running, b->running, sizeof(int), hipMemcpyDeviceToHost, b->stream));
         BHIP(b, hipStreamSynchronize(b->stream));
         a.init = 0;
