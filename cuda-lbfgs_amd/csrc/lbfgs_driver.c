@@ -117,6 +117,9 @@ struct lbfgs_ctx {
     int tc_n, tc_dphi_ok;
     double tc_a[LBK_TRIALS_NC], tc_f[LBK_TRIALS_NC], tc_dphi;
     int trial_passes;
+    /* the last two-loop iteration whose search ran trial passes here took three or more of them
+     * (tl_search: this iteration's search is such a one): the next one materialises d first */
+    int many_passes, tl_search;
     /* small n: the device-resident line search (lbk_search_dev) commits at the step it finds into
      * this slot (-1: no commit requested); committed: it did, this iteration; recommit_a0: a
      * launch that timed out may have left the first commit's outputs partly rewritten, so the
@@ -838,12 +841,16 @@ static int trial_batched(lbfgs_ctx* c, double alpha, int need_g, double* f, doub
     }
     /* d: the buffer once materialised; -g formed on the fly (one rank); the last second-loop
      * update formed on the fly for this iteration's first two trial passes, then materialised
-     * (3 vector reads per pass against 4 once for k_last + 2 per pass) */
+     * (3 vector reads per pass against 4 once for k_last + 2 per pass: 2 P + 6 for P >= 3 passes
+     * against 2 P + 4 with d materialised first). A search that took three or more passes in the
+     * last iteration that had any (a Wolfe search far from its first step takes a pass per step)
+     * is taken to do so again: d is materialised first, as without batching. The same bits. */
     int dm = LBK_D_BUF;
     if (!c->d_ready) {
+        if (c->dmode == LBK_D_TWOLOOP) c->tl_search = 1;
         if (c->dmode == LBK_D_NEG_G && c->geo->world == 1) {
             dm = LBK_D_NEG_G;
-        } else if (c->dmode == LBK_D_TWOLOOP && c->trial_passes < 2) {
+        } else if (c->dmode == LBK_D_TWOLOOP && c->trial_passes < 2 && !c->many_passes) {
             dm = LBK_D_TWOLOOP;
         } else {
             int rc = materialize_d(c);
@@ -1508,6 +1515,8 @@ static int iterate(lbfgs_ctx* c) {
     c->spec_valid = 0;
     c->cand_valid = 0;
     c->tc_n = 0;
+    if (c->tl_search && c->trial_passes > 0) c->many_passes = c->trial_passes >= 3;
+    c->tl_search = 0;
     c->trial_passes = 0;
     host_invalidate(c);
     c->hxx_valid = 0;
@@ -2516,6 +2525,7 @@ static int solver_init_at(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, 
     c->sp_adopted = c->sp_dropped = 0;
     c->search_launches = c->search_commits = 0;
     c->unfused = (flags & LBFGS_FLAG_UNFUSED) != 0;
+    c->many_passes = c->tl_search = 0;
     c->batch = 1;
     {
         const char* e = getenv("LBFGS_BATCH");
@@ -2877,6 +2887,7 @@ int lbfgs_line_search(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int 
     c->cand_valid = 0;
     c->tc_n = 0;
     c->trial_passes = 0;
+    c->many_passes = c->tl_search = 0;
     c->cuda = 0;
     c->obj = objective;
     c->ls = line_search;
