@@ -19,6 +19,10 @@
 // are the host's expressions on the same totals, which every thread holds (uniform branches). The
 // result of every problem is therefore bit for bit lbfgs_minimize's for that problem alone.
 // Nothing here waits on another workgroup, a flag or the host: no grid barrier, no time-out.
+//
+// x0 and x are rows at a stride (BatchArgs xin / xout), A's rows and b likewise (BatchDenseArgs lda /
+// ldb): the batch's own buffers for the host forms, a caller's device buffers as they are for
+// lbfgs_batch_minimize_device and lbfgs_batch_set_dense_quadratics_device.
 #include "lbfgs_hip.h"
 #include "lbfgs_kernels_impl.h"
 
@@ -50,7 +54,9 @@ struct BatchArgs {
     int B, m, iters, max_iterations, trace, init, tr_cap;
     int64_t vstride, pstride;  // doubles per vector / per problem
     double* base;              // element 0 of vector 0 of problem 0
-    double* xio;               // [B][n]: x0 in, x out
+    const double* xin;         // x0 in: problem p's n doubles at xin + p * ldxin (ldxin 0: one x0 for all)
+    double* xout;              // x out: problem p's at xout + p * ldxout. The batch's own [B][n] for both
+    int64_t ldxin, ldxout;     // (lbfgs_batch_minimize), or the caller's rows (lbfgs_batch_minimize_device)
     BatchState* st;
     double* tr;                // [B][3][tr_cap]: f, |g|, alpha
     int* running;              // set when a problem is unfinished at the end of the launch
@@ -175,7 +181,8 @@ __device__ __forceinline__ bool batch_enter(const BatchArgs& a, const BatchView&
     S.status = LBFGS_STATUS_RUNNING;
     S.h_min = S.h_max = -1;
     double* x0 = V.vec(0);
-    for (int64_t i = threadIdx.x; i < n; i += LB_BLOCK) x0[i] = a.xio[(int64_t)p * n + i];
+    const double* xin = a.xin + (int64_t)p * a.ldxin;
+    for (int64_t i = threadIdx.x; i < n; i += LB_BLOCK) x0[i] = xin[i];
     batch_stage_sync();
     return false;
 }
@@ -359,7 +366,8 @@ __device__ __forceinline__ void batch_leave(const BatchArgs& a, const BatchView&
                                             const BatchState& S) {
     if (S.status != LBFGS_STATUS_RUNNING) {
         const double* xc = V.vec(S.flip ? 2 : 0);
-        for (int64_t i = threadIdx.x; i < n; i += LB_BLOCK) a.xio[(int64_t)p * n + i] = xc[i];
+        double* xout = a.xout + (int64_t)p * a.ldxout;
+        for (int64_t i = threadIdx.x; i < n; i += LB_BLOCK) xout[i] = xc[i];
     }
     if (threadIdx.x == 0) {
         a.st[p] = S;
@@ -515,10 +523,11 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) 
 // from the evaluation.
 // ---------------------------------------------------------------------------------------
 struct BatchDenseArgs {
-    const double* A;   // [B][n][n], or one [n][n] when astride is 0
-    const double* b;   // [B][n]
+    const double* A;   // problem p's row i at A + p * astride + i * lda; astride 0: one matrix for all
+    const double* b;   // problem p's at b + p * ldb; ldb 0: one b for all
     double* xbase;     // element 0 of problem 0's terms vector t; its trial gradient gt one vector behind
-    int64_t astride;   // n * n, or 0: every problem reads the same matrix
+    int64_t astride;   // the batch's own copies: n * n (or 0), lda = ldb = n; a caller's buffers
+    int64_t lda, ldb;  // (lbfgs_batch_set_dense_quadratics_device): the caller's strides
 };
 
 // the host's caches of an external objective (host_point_issue / host_f_at / host_g_at with
@@ -548,13 +557,13 @@ __device__ __forceinline__ void dense_point(double* z, const double* x, const do
 // ascending, then the wave butterfly. The row index is wave-uniform and the loop holds no barrier,
 // so with fewer rows than waves the idle waves fall through to the barrier behind it.
 __device__ __forceinline__ void dense_rows(const double* __restrict__ A, const double* __restrict__ b, const double* z,
-                                           double* g, double* tv, int64_t n) {
+                                           double* g, double* tv, int64_t n, int64_t lda) {
     int t = threadIdx.x;
     asm volatile("" : "+v"(t));
     const int lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
     for (int64_t i = w; i < n; i += 4) {
-        const double* __restrict__ a = A + i * n;
+        const double* __restrict__ a = A + i * lda;
         double v = 0.0;
         for (int64_t j = lane; j < n; j += 64) v = fma(a[j], z[j], v);
         v = wave_sum(v);
@@ -581,12 +590,12 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, Bat
         const BatchView V = batch_view(a, p);
         double* const d = V.d();
         const double* const Ap = dq.A + (int64_t)p * dq.astride;
-        const double* const bp = dq.b + (int64_t)p * n;
+        const double* const bp = dq.b + (int64_t)p * dq.ldb;
         double* const tv = dq.xbase + (int64_t)p * 2 * a.vstride;
         double* const gt = tv + a.vstride;
         // lbk_dense_eval: the rows at z with the gradient into gout, then f (and gout . gout) from the terms
         auto eval = [&](const double* z, double* gout, double (&t2)[2]) {
-            dense_rows(Ap, bp, z, gout, tv, n);
+            dense_rows(Ap, bp, z, gout, tv, n, dq.lda);
             batch_pass<2>(OpTermsDot<false>{tv, gout}, geo, L, t2);
             S.vecs += (double)n + 5.0;
         };
@@ -766,6 +775,12 @@ struct lbfgs_batch {
     double* dq_x;
     size_t dq_A_doubles;  // capacity of dq_A
     bool dq_set, dq_shared;
+    // ... or, by reference, a caller's device buffers (lbfgs_batch_set_dense_quadratics_device):
+    // nothing of them is copied, dq_A and dq_b are released, t and gt stay the batch's own
+    bool dq_ref;
+    const double* ref_A;
+    const double* ref_b;
+    int64_t ref_astride, ref_lda, ref_ldb;
     hipStream_t stream;
     std::vector<BatchState> hst;  // the states after the last solve
     std::vector<double> htr;      // its traces (LBFGS_FLAG_TRACE)
@@ -783,6 +798,57 @@ struct lbfgs_batch {
             return LBFGS_ERR_HIP;                                                               \
         }                                                                                       \
     } while (0)
+
+// The per-problem terms vector t and trial gradient gt of the dense objective, allocated once.
+static int batch_dense_scratch(lbfgs_batch* b, const char* who) {
+    if (b->dq_x) return 0;
+    const size_t xbytes = sizeof(double) * 2 * (size_t)b->vstride * (size_t)b->B;
+    if (hipMalloc((void**)&b->dq_x, xbytes) != hipSuccess) {  // the batch stays usable for the stencil objectives
+        (void)hipGetLastError();
+        b->dq_x = nullptr;
+        snprintf(b->err, sizeof b->err, "%s: out of device memory", who);
+        return LBFGS_ERR_NOMEM;
+    }
+    // ghost cells and padding are zero and stay zero, as the batch's other vectors'
+    if (hipMemsetAsync(b->dq_x, 0, xbytes, b->stream) != hipSuccess || hipStreamSynchronize(b->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(b->dq_x);
+        b->dq_x = nullptr;
+        snprintf(b->err, sizeof b->err, "%s: hipMemsetAsync failed", who);
+        return LBFGS_ERR_HIP;
+    }
+    return 0;
+}
+
+// A caller's buffer of `doubles` doubles at p: 8-byte aligned, plain device memory of the batch's
+// device (pinned host, managed and other devices' memory are refused), and, where the runtime
+// knows the allocation, inside it from the first byte to the last. A wrong pointer ends here as a
+// status, not as a fault in a kernel.
+static bool batch_caller_range(const lbfgs_batch* b, const double* p, int64_t doubles) {
+    if (!p || ((uintptr_t)p & 7) != 0 || doubles < 1) return false;
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (at.type != hipMemoryTypeDevice || at.isManaged || at.device != b->device) return false;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;  // an allocation the runtime gives no extent for: the attributes are the check
+    }
+    return (const char*)p >= (const char*)base &&
+           (const char*)p + sizeof(double) * (size_t)doubles <= (const char*)base + size;
+}
+
+// the doubles from the first element of row 0 to the last of row rows - 1 (ld 0: one row)
+static int64_t batch_span(int64_t rows, int64_t ld, int64_t n) { return (ld ? (rows - 1) * ld : 0) + n; }
+
+static bool batch_overlap(const double* p, int64_t np, const double* q, int64_t nq) {
+    return (uintptr_t)p < (uintptr_t)(q + nq) && (uintptr_t)q < (uintptr_t)(p + np);
+}
 
 extern "C" {
 
@@ -886,20 +952,14 @@ int lbfgs_batch_set_dense_quadratics(lbfgs_batch* b, const double* A, int shared
     BHIP(b, hipSetDevice(b->device));
     const size_t nn = (size_t)b->n * (size_t)b->n, B = (size_t)b->B;
     const size_t a_doubles = shared_A ? nn : nn * B;
-    const size_t xbytes = sizeof(double) * 2 * (size_t)b->vstride * B;
     b->dq_set = false;
+    b->dq_ref = false;  // a caller's buffers are referenced no longer
+    b->ref_A = b->ref_b = nullptr;
     bool ok = true;
     if (!b->dq_b) ok = hipMalloc((void**)&b->dq_b, sizeof(double) * (size_t)b->n * B) == hipSuccess;
-    if (ok && !b->dq_x) {
-        ok = hipMalloc((void**)&b->dq_x, xbytes) == hipSuccess;
-        // ghost cells and padding are zero and stay zero, as the batch's other vectors'
-        if (ok && hipMemsetAsync(b->dq_x, 0, xbytes, b->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(b->dq_x);
-            b->dq_x = nullptr;
-            snprintf(b->err, sizeof b->err, "lbfgs_batch_set_dense_quadratics: hipMemsetAsync failed");
-            return LBFGS_ERR_HIP;
-        }
+    if (ok) {
+        const int rc = batch_dense_scratch(b, "lbfgs_batch_set_dense_quadratics");
+        if (rc != 0) return rc;
     }
     if (ok && b->dq_A_doubles < a_doubles) {
         if (b->dq_A) (void)hipFree(b->dq_A);
@@ -921,17 +981,65 @@ int lbfgs_batch_set_dense_quadratics(lbfgs_batch* b, const double* A, int shared
     return 0;
 }
 
-int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const lbfgs_constants* k,
-                         const double* x0_host, double* x_out_host, int max_iterations, double tolerance,
-                         unsigned flags, lbfgs_result* out) {
+int lbfgs_batch_set_dense_quadratics_device(lbfgs_batch* b, const double* A_dev, int64_t a_batch_stride, int64_t lda,
+                                            const double* b_dev, int64_t ldb) {
     if (!b) return LBFGS_ERR_BAD_ARG;
     b->err[0] = 0;
+    const int64_t n = b->n, B = b->B;
+    const char* bad = nullptr;
+    if (n > LBK_BATCH_DENSE_NMAX)
+        bad = "a batch of n <= 4096";
+    else if (!A_dev || !b_dev)
+        bad = "A_dev and b_dev";
+    else if (lda < n)
+        bad = "lda >= n";
+    else if (a_batch_stride != 0 && a_batch_stride < (n - 1) * lda + n)
+        bad = "a_batch_stride >= (n - 1) * lda + n, or 0 for one shared matrix";
+    else if (ldb != 0 && ldb < n)
+        bad = "ldb >= n, or 0 for one shared b";
+    if (!bad) {
+        BHIP(b, hipSetDevice(b->device));
+        if (!batch_caller_range(b, A_dev, batch_span(B, a_batch_stride, (n - 1) * lda + n)) ||
+            !batch_caller_range(b, b_dev, batch_span(B, ldb, n)))
+            bad = "A_dev and b_dev 8-byte aligned in device memory of the batch's device (not pinned host, not managed)";
+    }
+    if (bad) {  // the data set before, if any, stay as they are
+        snprintf(b->err, sizeof b->err, "lbfgs_batch_set_dense_quadratics_device: %s", bad);
+        return LBFGS_ERR_BAD_ARG;
+    }
+    b->dq_set = false;
+    const int rc = batch_dense_scratch(b, "lbfgs_batch_set_dense_quadratics_device");
+    if (rc != 0) return rc;
+    // the batch's own copies of an earlier host-form call are released: nothing holds a second A
+    BHIP(b, hipStreamSynchronize(b->stream));
+    if (b->dq_A) (void)hipFree(b->dq_A);
+    if (b->dq_b) (void)hipFree(b->dq_b);
+    b->dq_A = b->dq_b = nullptr;
+    b->dq_A_doubles = 0;
+    b->ref_A = A_dev;
+    b->ref_b = b_dev;
+    b->ref_astride = a_batch_stride;
+    b->ref_lda = lda;
+    b->ref_ldb = ldb;
+    b->dq_ref = true;
+    b->dq_set = true;
+    return 0;
+}
+
+}  // extern "C"
+
+// Both forms of lbfgs_batch_minimize: x0 is read at xin + p * ldxin and x written at xout + p * ldxout,
+// device memory both. x0_host / x_out_host (the host form only) are copied to and from the batch's
+// own xio around the launches; no hipMemcpy ever touches a caller's device buffer.
+static int batch_solve(lbfgs_batch* b, const char* who, int objective, int line_search, const lbfgs_constants* k,
+                       const double* xin, int64_t ldxin, double* xout, int64_t ldxout, const double* x0_host,
+                       double* x_out_host, int max_iterations, double tolerance, unsigned flags, lbfgs_result* out) {
     const bool dense = objective == LBFGS_OBJ_DENSE_QUAD && b->dq_set;
-    if (!x0_host || (!dense && (objective < LBFGS_OBJ_ROSENBROCK || objective > LBFGS_OBJ_QUAD_SEPARABLE)) ||
+    if ((!dense && (objective < LBFGS_OBJ_ROSENBROCK || objective > LBFGS_OBJ_QUAD_SEPARABLE)) ||
         line_search < LBFGS_LS_BACKTRACKING || line_search > LBFGS_LS_BACKTRACKING_WOLFE || max_iterations < 0 ||
         (flags & ~(LBFGS_FLAG_TRACE | LBFGS_FLAG_QUIET)) != 0) {
-        snprintf(b->err, sizeof b->err, "lbfgs_batch_minimize: device stencil objectives (the dense quadratic once "
-                 "its data is set), the four line searches, LBFGS_FLAG_TRACE / LBFGS_FLAG_QUIET only");
+        snprintf(b->err, sizeof b->err, "%s: device stencil objectives (the dense quadratic once "
+                 "its data is set), the four line searches, LBFGS_FLAG_TRACE / LBFGS_FLAG_QUIET only", who);
         return LBFGS_ERR_BAD_ARG;
     }
     const auto t0 = std::chrono::steady_clock::now();
@@ -957,7 +1065,10 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
     a.vstride = b->vstride;
     a.pstride = b->pstride;
     a.base = b->vecs + LBK_FRONT;
-    a.xio = b->xio;
+    a.xin = xin;
+    a.ldxin = ldxin;
+    a.xout = xout;
+    a.ldxout = ldxout;
     a.st = b->st;
     a.tr = trace ? b->tr : nullptr;
     a.running = b->running;
@@ -969,10 +1080,12 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
     BatchDenseArgs dq;
     memset(&dq, 0, sizeof dq);
     if (dense) {
-        dq.A = b->dq_A;
-        dq.b = b->dq_b;
+        dq.A = b->dq_ref ? b->ref_A : b->dq_A;
+        dq.b = b->dq_ref ? b->ref_b : b->dq_b;
         dq.xbase = b->dq_x + LBK_FRONT;
-        dq.astride = b->dq_shared ? 0 : b->n * b->n;
+        dq.astride = b->dq_ref ? b->ref_astride : b->dq_shared ? 0 : b->n * b->n;
+        dq.lda = b->dq_ref ? b->ref_lda : b->n;
+        dq.ldb = b->dq_ref ? b->ref_ldb : b->n;
     }
     // the one kernel of this solve and its arguments
     const void* const kern = dense ? (const void*)batch_dense_kernel(line_search)
@@ -989,8 +1102,9 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
     grid = std::min(grid, b->B);
     auto launch = [&] { return hipLaunchKernel(kern, dim3(grid), dim3(LB_BLOCK), kargs, 0, b->stream); };
     // x0 up (one contiguous copy; each workgroup moves its problem's x0 into the vector layout)
-    BHIP(b, hipMemcpyAsync(b->xio, x0_host, sizeof(double) * (size_t)b->n * (size_t)b->B, hipMemcpyHostToDevice,
-                           b->stream));
+    if (x0_host)
+        BHIP(b, hipMemcpyAsync(b->xio, x0_host, sizeof(double) * (size_t)b->n * (size_t)b->B, hipMemcpyHostToDevice,
+                               b->stream));
     // every launch takes each unfinished problem at least one iteration further, or ends it
     const long long max_launches = (long long)max_iterations / a.iters + 2;
     long long launches = 0;
@@ -1004,7 +1118,7 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
         ++launches;
         if (!running) break;
         if (launches >= max_launches) {
-            snprintf(b->err, sizeof b->err, "lbfgs_batch_minimize: problems unfinished after %lld launches", launches);
+            snprintf(b->err, sizeof b->err, "%s: problems unfinished after %lld launches", who, launches);
             return LBFGS_ERR_STATE;
         }
     }
@@ -1041,6 +1155,62 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
             r.h_max = s.h_min < 0 ? -1 : s.h_max;
         }
     return 0;
+}
+
+extern "C" {
+
+int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const lbfgs_constants* k,
+                         const double* x0_host, double* x_out_host, int max_iterations, double tolerance,
+                         unsigned flags, lbfgs_result* out) {
+    if (!b) return LBFGS_ERR_BAD_ARG;
+    b->err[0] = 0;
+    if (!x0_host) {
+        snprintf(b->err, sizeof b->err, "lbfgs_batch_minimize: x0_host");
+        return LBFGS_ERR_BAD_ARG;
+    }
+    return batch_solve(b, "lbfgs_batch_minimize", objective, line_search, k, b->xio, b->n, b->xio, b->n, x0_host,
+                       x_out_host, max_iterations, tolerance, flags, out);
+}
+
+int lbfgs_batch_minimize_device(lbfgs_batch* b, int objective, int line_search, const lbfgs_constants* k,
+                                const double* x0_dev, int64_t ldx0, double* x_out_dev, int64_t ldx, int max_iterations,
+                                double tolerance, unsigned flags, lbfgs_result* out) {
+    if (!b) return LBFGS_ERR_BAD_ARG;
+    b->err[0] = 0;
+    const int64_t n = b->n, B = b->B;
+    const char* bad = nullptr;
+    if (!x0_dev)
+        bad = "x0_dev";
+    else if (ldx0 != 0 && ldx0 < n)
+        bad = "ldx0 >= n, or 0 for one x0 shared by every problem";
+    else if (x_out_dev && ldx < n)
+        bad = "ldx >= n";
+    const int64_t span0 = batch_span(B, ldx0, n), span = batch_span(B, ldx, n);
+    if (!bad) {
+        BHIP(b, hipSetDevice(b->device));
+        if (!batch_caller_range(b, x0_dev, span0) || (x_out_dev && !batch_caller_range(b, x_out_dev, span)))
+            bad = "x0_dev and x_out_dev 8-byte aligned in device memory of the batch's device (not pinned host, not "
+                  "managed)";
+    }
+    if (!bad && x_out_dev) {
+        // in place (the same rows: a problem's row is read at its entry and written at its exit by
+        // the same workgroup) or disjoint from x0; disjoint from the A and b the batch refers to
+        const bool in_place = x_out_dev == x0_dev && ldx == ldx0;
+        if (!in_place && batch_overlap(x_out_dev, span, x0_dev, span0))
+            bad = "x_out_dev either x0_dev itself with ldx == ldx0 >= n or not overlapping it";
+        else if (b->dq_set && b->dq_ref &&
+                 (batch_overlap(x_out_dev, span, b->ref_A, batch_span(B, b->ref_astride, (n - 1) * b->ref_lda + n)) ||
+                  batch_overlap(x_out_dev, span, b->ref_b, batch_span(B, b->ref_ldb, n))))
+            bad = "x_out_dev not overlapping the A and b set by lbfgs_batch_set_dense_quadratics_device";
+    }
+    if (bad) {
+        snprintf(b->err, sizeof b->err, "lbfgs_batch_minimize_device: %s", bad);
+        return LBFGS_ERR_BAD_ARG;
+    }
+    // without x_out_dev the kernel's x goes to the batch's own rows
+    return batch_solve(b, "lbfgs_batch_minimize_device", objective, line_search, k, x0_dev, ldx0,
+                       x_out_dev ? x_out_dev : b->xio, x_out_dev ? ldx : n, nullptr, nullptr, max_iterations, tolerance,
+                       flags, out);
 }
 
 int lbfgs_batch_trace_len(const lbfgs_batch* b, int problem) {

@@ -167,6 +167,9 @@ def lib():
     L.lbfgs_batch_events_get.argtypes = [vp, C.c_int, C.POINTER(BatchEvents)]
     L.lbfgs_batch_dense_plan.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.lbfgs_batch_set_dense_quadratics.argtypes = [vp, vp, C.c_int, vp]
+    L.lbfgs_batch_minimize_device.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Constants), vp, C.c_int64, vp, C.c_int64,
+                                              C.c_int, C.c_double, C.c_uint, C.POINTER(Result)]
+    L.lbfgs_batch_set_dense_quadratics_device.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64]
     L.lbfgs_set_device_objective.argtypes = [vp, C.POINTER(DeviceFn)]
     L.lbfgs_minimize_device.argtypes = [vp, C.c_int, C.POINTER(HostFn), C.c_int, C.POINTER(Constants),
                                         vp, vp, C.c_int, C.c_double, C.c_uint, C.POINTER(Result)]
@@ -196,6 +199,7 @@ EXPORTED_SYMBOLS = [
     "lbfgs_batch_plan", "lbfgs_batch_create", "lbfgs_batch_destroy", "lbfgs_batch_last_error",
     "lbfgs_batch_set_launch", "lbfgs_batch_minimize", "lbfgs_batch_trace_len", "lbfgs_batch_trace_get",
     "lbfgs_batch_events_get", "lbfgs_batch_dense_plan", "lbfgs_batch_set_dense_quadratics",
+    "lbfgs_batch_minimize_device", "lbfgs_batch_set_dense_quadratics_device",
     "lbfgs_set_device_objective", "lbfgs_minimize_device", "lbfgs_solver_init_device", "lbfgs_get_x_device",
     "lbfgs_reducer_create", "lbfgs_reducer_destroy", "lbfgs_reducer_dot",
 ]
@@ -330,7 +334,8 @@ class Batch:
     """
 
     def __init__(self, n, m, batch, device=0):
-        self.n, self.m, self.batch = int(n), int(m), int(batch)
+        self.n, self.m, self.batch, self.device = int(n), int(m), int(batch), int(device)
+        self._dq_refs = None  # the tensors set_dense_quadratics_device refers to
         h = C.c_void_p()
         rc = lib().lbfgs_batch_create(C.byref(h), self.n, self.m, self.batch, int(device))
         if rc != 0:
@@ -343,6 +348,7 @@ class Batch:
         if getattr(self, "h", None):
             lib().lbfgs_batch_destroy(self.h)
             self.h = None
+        self._dq_refs = None
 
     def __enter__(self):
         return self
@@ -386,6 +392,80 @@ class Batch:
                                                     b.ctypes.data_as(C.c_void_p))
         if rc != 0:
             self._err("lbfgs_batch_set_dense_quadratics", rc)
+        self._dq_refs = None  # the batch reads its own copies now
+
+    def _rows(self, t, what, shapes, shared_ok):
+        """Checks a float64 CUDA tensor on the batch's device whose last stride is 1 and whose other
+        strides are >= n (or, where shared_ok, 0 in dimension 0, the batch's); returns its strides. Never a
+        copy: the library works on the tensor's own memory."""
+        torch = _torch()
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: a torch tensor is required, got {type(t).__name__}")
+        if t.dtype != torch.float64:
+            raise TypeError(f"{what}: dtype float64 is required, got {t.dtype}")
+        if not t.is_cuda or (t.device.index or 0) != self.device:
+            raise ValueError(f"{what}: a CUDA tensor on device {self.device} is required, got {t.device}")
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"{what}: shape {tuple(t.shape)}, expected " + " or ".join(str(s) for s in shapes))
+        st = t.stride()
+        if st[-1] != 1 and self.n > 1:
+            raise ValueError(f"{what}: the last dimension must have stride 1, got strides {st} (no copy is made)")
+        for d in range(t.dim() - 1):
+            size, ok0 = t.shape[d], shared_ok and d == 0
+            if size > 1 and not (st[d] >= self.n or (ok0 and st[d] == 0)):
+                raise ValueError(f"{what}: stride {st[d]} of dimension {d} must be >= n = {self.n}"
+                                 + (" (or 0, an expanded row)" if ok0 else ""))
+        return st
+
+    def set_dense_quadratics_device(self, A, b):
+        """set_dense_quadratics BY REFERENCE to CUDA tensors: A of shape (batch, n, n) with last stride
+        1, row stride >= n and any batch stride that keeps the matrices apart (0, from expand, or a 2-D
+        (n, n) tensor: one matrix shared by every problem); b of shape (batch, n), last stride 1, row
+        stride >= n or 0. float64, on the batch's device. Nothing is copied (so nothing is made
+        contiguous either): every later "dense" solve reads the tensors' memory as it then is, and the
+        object keeps references to both until they are replaced or close() is called."""
+        torch = _torch()
+        n, B = self.n, self.batch
+        sa = self._rows(A, "set_dense_quadratics_device: A", ((B, n, n), (n, n)), getattr(A, "ndim", 0) == 3)
+        sb = self._rows(b, "set_dense_quadratics_device: b", ((B, n),), True)
+        lda = sa[-2] if n > 1 else n
+        abs_ = 0 if A.dim() == 2 else (sa[0] if B > 1 else (n - 1) * lda + n)
+        if abs_ != 0 and abs_ < (n - 1) * lda + n:
+            raise ValueError(f"set_dense_quadratics_device: A: batch stride {abs_} must be >= (n - 1) * {lda} + n "
+                             "(matrices that do not interleave), or 0")
+        ldb = sb[0] if B > 1 else n
+        torch.cuda.current_stream(self.device).synchronize()  # the caller's work on A and b is complete
+        rc = lib().lbfgs_batch_set_dense_quadratics_device(self.h, A.data_ptr(), int(abs_), int(lda), b.data_ptr(),
+                                                           int(ldb))
+        if rc != 0:
+            self._err("lbfgs_batch_set_dense_quadratics_device", rc)
+        self._dq_refs = (A, b)
+
+    def minimize_device(self, objective, X0, line_search="backtracking", max_iterations=1000, tolerance=1e-5,
+                        consts=None, trace=False, flags=0, out=None):
+        """minimize() with X0 and the result in device memory: float64 CUDA tensors of shape (batch, n) on
+        the batch's device with last stride 1; X0 with any row stride >= n or 0 (an expanded row), out
+        with a row stride >= n (a new contiguous tensor when None; X0 itself solves in place). A storage
+        offset is fine. No copy is made. Returns minimize()'s dictionary, bit for bit, with x the tensor."""
+        torch = _torch()
+        n, B = self.n, self.batch
+        s0 = self._rows(X0, "minimize_device: X0", ((B, n),), True)
+        if out is not None:
+            self._rows(out, "minimize_device: out", ((B, n),), False)
+        X = out if out is not None else torch.empty((B, n), dtype=torch.float64, device=X0.device)
+        ldx0 = s0[0] if B > 1 else n
+        ldx = X.stride(0) if B > 1 else n
+        torch.cuda.current_stream(self.device).synchronize()  # the caller's work on X0 (and A, b) is complete
+        res = (Result * B)()
+        k = consts if consts is not None else constants()
+        fl = FLAG_QUIET | (FLAG_TRACE if trace else 0) | int(flags)
+        obj = OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        rc = lib().lbfgs_batch_minimize_device(self.h, obj, LINE_SEARCHES[line_search], C.byref(k), X0.data_ptr(),
+                                               int(ldx0), X.data_ptr(), int(ldx), int(max_iterations), float(tolerance),
+                                               fl, res)
+        if rc < 0:
+            self._err("lbfgs_batch_minimize_device", rc)
+        return self._results(res, X, trace)
 
     def minimize(self, objective, X0, line_search="backtracking", max_iterations=1000, tolerance=1e-5,
                  consts=None, trace=False, flags=0, out=None):
@@ -406,6 +486,9 @@ class Batch:
                                         int(max_iterations), float(tolerance), fl, res)
         if rc < 0:
             self._err("lbfgs_batch_minimize", rc)
+        return self._results(res, X, trace)
+
+    def _results(self, res, X, trace):
         col = lambda name, dt: np.array([getattr(r, name) for r in res], dtype=dt)  # noqa: E731
         code = col("status", np.int64)
         d = dict(x=X, f=col("f", np.float64), gnorm=col("gnorm", np.float64), iterations=col("iterations", np.int64),

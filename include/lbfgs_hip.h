@@ -436,6 +436,40 @@ int lbfgs_batch_dense_plan(int64_t n, int m, int batch, int shared_A, double* by
  * (the batch object stays usable for the stencil objectives). */
 int lbfgs_batch_set_dense_quadratics(lbfgs_batch* b, const double* A, int shared_A, const double* bvec);
 
+/* The batch with x0, x, A and b in device memory. All strides are in doubles; the
+ * buffers are caller-owned, unpadded, 8-byte aligned and no more. No hipMemcpy touches a caller's
+ * buffer: the solve kernels read and write the caller's rows themselves (out, the trace and the
+ * running flag keep their copies from library-owned memory).
+ *
+ * lbfgs_batch_minimize_device is lbfgs_batch_minimize in everything but where x0 and x live
+ * (objectives, searches, flags, limits, out, traces, events, the 4096-trial cap; results bit for bit
+ * the same). Problem p's x0 is the n doubles at x0_dev + p*ldx0, ldx0 >= n, or ldx0 == 0 for one x0
+ * shared by every problem; its x goes to x_out_dev + p*ldx, ldx >= n (x_out_dev may be NULL). The
+ * kernel reads exactly [0, n) of each x0 row and writes exactly [0, n) of each x row. Solving in
+ * place, x_out_dev == x0_dev with ldx == ldx0 >= n, is allowed (a problem's row is read at its entry
+ * and written at its exit by the same workgroup); any other overlap of the x range with the x0 range,
+ * or with the A and b ranges the batch refers to, is LBFGS_ERR_BAD_ARG. The caller's work on x0_dev
+ * (and on referenced A and b) is complete at the call; x_out_dev is complete on return.
+ *
+ * lbfgs_batch_set_dense_quadratics_device works BY REFERENCE: problem p's row i is the n doubles at
+ * A_dev + p*a_batch_stride + i*lda, lda >= n, a_batch_stride == 0 for one shared matrix and otherwise
+ * >= (n-1)*lda + n; b_p is at b_dev + p*ldb, ldb >= n or 0. Nothing is copied: every later dense solve
+ * of the batch (either form of minimize) reads these buffers, until another setter call (either
+ * form) replaces them or the batch is destroyed. The caller keeps them alive and may change their
+ * contents between solves; the next solve sees the new data. The call allocates only the per-problem
+ * t and gt vectors and releases the batch's own copies of A and b if an earlier host-form call made
+ * them (a later host-form call allocates them again). LBFGS_ERR_BAD_ARG for n > 4096.
+ *
+ * Both refuse with LBFGS_ERR_BAD_ARG, a message in lbfgs_batch_last_error and nothing launched:
+ * null pointers where one is required, strides outside the ranges above, the overlaps above, and a
+ * pointer that hipPointerGetAttributes does not report as device memory of the batch's device
+ * (pinned host, managed and other devices' memory included). */
+int lbfgs_batch_minimize_device(lbfgs_batch* b, int objective, int line_search, const lbfgs_constants* k,
+                                const double* x0_dev, int64_t ldx0, double* x_out_dev, int64_t ldx,
+                                int max_iterations, double tolerance, unsigned flags, lbfgs_result* out);
+int lbfgs_batch_set_dense_quadratics_device(lbfgs_batch* b, const double* A_dev, int64_t a_batch_stride,
+                                            int64_t lda, const double* b_dev, int64_t ldb);
+
 /* ---- canonical reductions on caller-owned device buffers -------------------------------- */
 /* For objectives evaluated on the device (LBFGS_OBJ_DEVICE): the sum of their per-element terms in
  * the solver's canonical fixed order, so that f is reproducible run to run and
