@@ -1,9 +1,9 @@
 // lbfgs_kernels_batch.hip — the batched small-n solver (lbfgs_batch_*, include/lbfgs_hip.h): B
-// independent problems that share n, m, objective, line search, constants, tolerance and iteration
-// limit and differ in x0, each solved by ONE workgroup that runs the whole loop of iterate()
-// (lbfgs_driver.c) on the device. A translation unit of its own: twelve large kernels for the stencil
-// objectives (k_batch_solve), and four for dense quadratics with each problem's own A and b
-// (k_batch_solve_dense, further down: the driver's external-objective path).
+// independent problems that share n (or not: ragged batches, below), m, objective, line search,
+// constants, tolerance and iteration limit and differ in x0, each solved by ONE workgroup that runs
+// the whole loop of iterate() (lbfgs_driver.c) on the device. A translation unit of its own: twelve
+// large kernels for the stencil objectives (k_batch_solve), and four for dense quadratics with each
+// problem's own A and b (k_batch_solve_dense, further down: the driver's external-objective path).
 //
 // The two kernel templates follow different branches of iterate() and stay two kernels. What the
 // branches have in common is written once, as force-inlined stages that both call (batch_enter,
@@ -23,6 +23,12 @@
 // x0 and x are rows at a stride (BatchArgs xin / xout), A's rows and b likewise (BatchDenseArgs lda /
 // ldb): the batch's own buffers for the host forms, a caller's device buffers as they are for
 // lbfgs_batch_minimize_device and lbfgs_batch_set_dense_quadratics_device.
+//
+// A ragged batch (lbfgs_batch_create_ragged) gives every problem its own n: the
+// problems' vectors lie packed one behind another, a table in device memory has a row per problem
+// (BatchRow), and the workgroup forms its problem's geometry, vectors and rows from that row inside
+// the problem loop; passes, stages and searches are the same code. Its kernels are a second
+// compilation of the two kernel bodies (sixteen more), so a uniform batch runs what it always ran.
 #include "lbfgs_hip.h"
 #include "lbfgs_kernels_impl.h"
 
@@ -63,6 +69,61 @@ struct BatchArgs {
     double tol;
     lbfgs_constants K;
 };
+
+// A ragged batch (lbfgs_batch_create_ragged): problem p has its own size n_p and
+// its vectors lie packed behind those of the problems before it. One row per problem, written once
+// at creation; every offset is in doubles.
+struct BatchRow {
+    int64_t n;        // n_p
+    int64_t vbase;    // element 0 of vector 0 of problem p, from BatchArgs::base
+    int64_t vstride;  // doubles per vector: lbk_vec_alloc's layout for n_p
+    int64_t off;      // packed offset of x0 / x / b: the sum of n_q over q < p
+    int64_t off2;     // packed offset of A: the sum of n_q * n_q over q < p
+    int64_t xbase;    // dense: problem p's terms vector t, from BatchDenseArgs::xbase
+};
+
+// The last argument of a ragged batch's kernels; a uniform batch's do not have it.
+struct BatchRagged {
+    const BatchRow* tab;  // [B]
+    const int* order;     // [B]: the i-th problem taken is order[i] (largest first); null: i itself
+};
+
+// The problem a workgroup is on: its index, and on a ragged batch its row of the table.
+struct BatchProb {
+    int p;
+    const BatchRow* row;
+};
+
+// A table value: the same in every thread of the workgroup, so it belongs in SGPRs. The load is
+// through the constant address space (a scalar load; the table is written before the first launch
+// and never by a kernel), and the halves pass through readfirstlane so that the compiler knows the
+// uniformity wherever it has lost sight of it.
+__device__ __forceinline__ int64_t batch_row_ld(const int64_t* q) {
+    const int64_t v = *(const __attribute__((address_space(4))) int64_t*)q;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+    return (int64_t)(((unsigned long long)hi << 32) | lo);
+}
+
+template <bool RAGGED>
+__device__ __forceinline__ BatchProb batch_prob(const BatchRagged& rg, int i) {
+    if (!RAGGED) return {i, nullptr};
+    const int p =
+        rg.order ? __builtin_amdgcn_readfirstlane(*(const __attribute__((address_space(4))) int*)(rg.order + i)) : i;
+    return {p, rg.tab + p};
+}
+
+// The geometry of the problem: the batch's, with n, n_loc and nseg the problem's own on a ragged batch.
+template <bool RAGGED>
+__device__ __forceinline__ Geo batch_geo(const Geo& geo, const BatchProb& P) {
+    Geo g = geo;
+    if (RAGGED) {
+        const int64_t n = batch_row_ld(&P.row->n);
+        g.n = g.n_loc = n;
+        g.nseg = (n + 511) / 512;
+    }
+    return g;
+}
 
 // A problem's scalars are the same in every thread of its workgroup. Held in registers they (the
 // state, the search's variables and caches, the commit's totals: some 250 values) are live across
@@ -158,8 +219,21 @@ struct BatchView {
     __device__ __forceinline__ double* y(int pair) const { return vec(8 + 2 * pair); }
 };
 
-__device__ __forceinline__ BatchView batch_view(const BatchArgs& a, int p) {
+template <bool RAGGED>
+__device__ __forceinline__ BatchView batch_view(const BatchArgs& a, const BatchProb& P) {
+    const int p = P.p;
+    if (RAGGED)
+        return {a.base + batch_row_ld(&P.row->vbase), batch_row_ld(&P.row->vstride),
+                a.trace ? a.tr + (int64_t)p * 3 * a.tr_cap : nullptr};
     return {a.base + (int64_t)p * a.pstride, a.vstride, a.trace ? a.tr + (int64_t)p * 3 * a.tr_cap : nullptr};
+}
+
+// Problem p's row of a batch of rows: at p * ld, or on a ragged batch with ld == LBFGS_BATCH_PACKED at
+// the problem's packed offset.
+template <bool RAGGED>
+__device__ __forceinline__ int64_t batch_row_at(const BatchProb& P, int64_t ld) {
+    if (RAGGED && ld < 0) return batch_row_ld(&P.row->off);
+    return (int64_t)P.p * ld;
 }
 
 // one iteration's vectors: which of x/xn and g/gn is current, and the spare pair the commit fills
@@ -170,7 +244,10 @@ struct BatchIter {
 // Entering a problem. A new solve starts a fresh record and moves x0 into the vector layout (the
 // kernel then evaluates there); a later launch loads the record. True when the problem finished in
 // an earlier launch (uniform).
-__device__ __forceinline__ bool batch_enter(const BatchArgs& a, const BatchView& V, int p, int64_t n, BatchState& S) {
+template <bool RAGGED>
+__device__ __forceinline__ bool batch_enter(const BatchArgs& a, const BatchView& V, const BatchProb& P, int64_t n,
+                                            BatchState& S) {
+    const int p = P.p;
     if (!a.init) {
         const BatchState* G = a.st + p;
         if (G->status != LBFGS_STATUS_RUNNING) return true;
@@ -181,7 +258,7 @@ __device__ __forceinline__ bool batch_enter(const BatchArgs& a, const BatchView&
     S.status = LBFGS_STATUS_RUNNING;
     S.h_min = S.h_max = -1;
     double* x0 = V.vec(0);
-    const double* xin = a.xin + (int64_t)p * a.ldxin;
+    const double* xin = a.xin + batch_row_at<RAGGED>(P, a.ldxin);
     for (int64_t i = threadIdx.x; i < n; i += LB_BLOCK) x0[i] = xin[i];
     batch_stage_sync();
     return false;
@@ -362,11 +439,13 @@ __device__ __forceinline__ void batch_accept(int m, BatchState& S, const BatchWa
 }
 
 // Leaving a problem: x out when it finished in this launch, the record stored, the running flag.
-__device__ __forceinline__ void batch_leave(const BatchArgs& a, const BatchView& V, int p, int64_t n,
+template <bool RAGGED>
+__device__ __forceinline__ void batch_leave(const BatchArgs& a, const BatchView& V, const BatchProb& P, int64_t n,
                                             const BatchState& S) {
+    const int p = P.p;
     if (S.status != LBFGS_STATUS_RUNNING) {
         const double* xc = V.vec(S.flip ? 2 : 0);
-        double* xout = a.xout + (int64_t)p * a.ldxout;
+        double* xout = a.xout + batch_row_at<RAGGED>(P, a.ldxout);
         for (int64_t i = threadIdx.x; i < n; i += LB_BLOCK) xout[i] = xc[i];
     }
     if (threadIdx.x == 0) {
@@ -377,140 +456,18 @@ __device__ __forceinline__ void batch_leave(const BatchArgs& a, const BatchView&
 
 // The fused stencil branch of iterate(): the first trial at initial_step rides the commit, the
 // search starts from that pass's totals, and the commit is repeated only at another step.
+// One body, two argument lists (lbfgs_kernels_batch_solve.h says why).
 template <int OBJ, int LS>
-__global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo) {
-    __shared__ BatchLds L;
-    constexpr bool FG = LS == 2 || LS == 3;
-    constexpr bool CAND = LS == 0;  // the backtracking search's second step rides the first commit
-    constexpr int NC = LBK_TRIALS_NC;
-    const int64_t n = geo.n;
-    BatchWave& W = L.wv[threadIdx.x >> 6];
-    BatchState& S = W.st;
-    lbk_search& s = W.s;
-    for (int p = blockIdx.x; p < a.B; p += gridDim.x) {
-        const BatchView V = batch_view(a, p);
-        if (batch_enter(a, V, p, n, S)) continue;
-        if (a.init) {  // f and g.g at x0 (lbfgs.cpp:29-30)
-            DirArgs da0 = {};
-            double t2[2];
-            batch_pass<2>(OpObjective<OBJ, true, true, false>{V.vec(0), da0, 0.0, V.vec(1), n, n}, geo, L, t2);
-            S.f_cur = t2[0];
-            S.gg = t2[1];
-            S.vecs = 2.0;
-        }
+__global__ __launch_bounds__(LB_BLOCK) void k_batch_solve(BatchArgs a, Geo geo_b) {
+    constexpr bool RAGGED = false;
+    const BatchRagged rg = {nullptr, nullptr};
+#include "lbfgs_kernels_batch_solve.h"
+}
 
-        for (int it = 0; it < a.iters; ++it) {
-            BatchIter I;
-            if (batch_iter_top(a, V, S, I)) break;
-            batch_direction(V, I, geo, L, S, W);
-
-            // ---- the fused first trial at a0 with the commit ----
-            const double a0 = a.K.initial_step;
-            const double cand = CAND ? a0 * a.K.backtracking_alpha : 0.0;
-            // how the direction is formed until d is materialised (k_commit's TWOLOOP / NEG_G)
-            auto dir_args = [&]() {
-                DirArgs dd = {};
-                dd.g = I.g;
-                dd.g_hi = LBK_GROUPS;
-                if (W.dmode == LBK_D_TWOLOOP) {
-                    dd.dsrc = V.r();
-                    dd.s = V.s(W.top);
-                    dd.coef = W.coef;
-                    dd.rho = W.rho_top;
-                }
-                return dd;
-            };
-            double gd;
-            for (bool fell_back = false;;) {  // the first trial at a0 and the commit, in one pass
-                const DirArgs dd = dir_args();
-                if (W.dmode == LBK_D_TWOLOOP) {
-                    batch_commit<OBJ, LBK_D_TWOLOOP, CAND>(geo, L, I.x, dd, a0, I.xn, I.gn, I.so, I.yo, cand, W.tot);
-                    S.vecs += 8.0;
-                } else {
-                    batch_commit<OBJ, LBK_D_NEG_G, CAND>(geo, L, I.x, dd, a0, I.xn, I.gn, I.so, I.yo, cand, W.tot);
-                    S.vecs += 6.0;
-                }
-                S.commits++;
-                gd = W.tot[LBK_C_GD];
-                if (!(gd >= 0) || fell_back) break;
-                S.ev[0]++;  // :146-153: not a descent direction, the gradient instead (once, as the host)
-                W.dmode = LBK_D_NEG_G;
-                fell_back = true;
-            }
-
-            // ---- the line search, with the host's caches of that pass ----
-            batch_search_begin(a, S, s, gd);
-            s.have_spec = 1;
-            s.spec_a = a0;
-            s.spec_f = W.tot[LBK_C_F];
-            s.spec_dphi = W.tot[LBK_C_DPHI];
-            if (CAND && cand > 0.0) {
-                s.have_cand = 1;
-                s.cand_a = cand;
-                s.cand_f = W.tot[LBK_C_FC];
-            }
-            W.d_ready = W.capped = W.passes = 0;
-            // d into its buffer before the first pass that reads it. Always inlined: left to the cost
-            // model it is a call in some of the twelve kernels, and what it captures (geo, the view,
-            // the iteration's vectors) then lives in scratch
-            auto need_d = [&]() __attribute__((always_inline)) {
-                if (W.d_ready) return;
-                batch_materialise_d(V, I, geo, L, S, W);
-                W.d_ready = 1;
-            };
-            auto trial = [&](double alpha, bool need_g, double& f, double& dphi) -> bool {
-                if (search_cached(s, alpha, need_g, f, dphi)) return true;
-                if (LS == 3 && W.passes >= LBK_BATCH_BTW_CAP) {  // the reference's loop has no bound of its own
-                    W.capped = 1;
-                    return false;
-                }
-                need_d();
-                W.passes++;
-                S.vecs += 2.0;
-                if (FG) {
-                    OpTrials<OBJ, LBK_D_BUF, 1, true, false> op{I.x, batch_buf_args(V, I), {alpha}, n, n};
-                    double tt[2];
-                    batch_pass<2>(op, geo, L, tt);
-                    search_note_fg(s, alpha, tt);
-                    f = tt[0];
-                    dphi = tt[1];
-                } else {
-                    OpTrials<OBJ, LBK_D_BUF, NC, false, false> op{I.x, batch_buf_args(V, I), {}, n, n};
-                    search_chain<LS>(s, alpha, op.a);
-                    double tt[NC];
-                    batch_pass<NC>(op, geo, L, tt);
-                    search_note_f(s, op.a, tt);
-                    f = tt[0];
-                }
-                return true;
-            };
-            search_loop<LS>(s, trial);
-            S.trials_f += s.passes_f;
-            S.trials_fg += s.passes_fg;
-            if (W.capped || !s.done) {
-                S.status = LBFGS_ERR_STATE;
-                break;
-            }
-            const double alpha = s.step;
-            batch_trace_step(a, V, S, alpha);
-
-            // ---- commit (:159-198): again at the search's step when that is not the first trial's ----
-            if (!(alpha == a0)) {
-                need_d();
-                batch_commit<OBJ, LBK_D_BUF, false>(geo, L, I.x, batch_buf_args(V, I), alpha, I.xn, I.gn, I.so, I.yo, 0.0,
-                                                    W.tot);
-                S.vecs += 7.0;
-                S.commits++;
-            }
-            S.f_cur = W.tot[LBK_C_F];
-            if (alpha < 1e-10) {  // :164-168
-                S.status = LBFGS_STATUS_LS_FAILED;
-                break;
-            }
-            batch_accept(a.m, S, W);
-        }
-        batch_leave(a, V, p, n, S);
-    }
+template <int OBJ, int LS>
+__global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_ragged(BatchArgs a, Geo geo_b, BatchRagged rg) {
+    constexpr bool RAGGED = true;
+#include "lbfgs_kernels_batch_solve.h"
 }
 
 // ---------------------------------------------------------------------------------------
@@ -577,180 +534,44 @@ __device__ __forceinline__ void dense_rows(const double* __restrict__ A, const d
 }
 
 template <int LS>
-__global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, BatchDenseArgs dq, Geo geo) {
-    __shared__ BatchDenseLds LD;
-    BatchLds& L = LD.L;
-    const int t = threadIdx.x;
-    const int64_t n = geo.n;
-    BatchWave& W = L.wv[t >> 6];
-    DenseWave& D = LD.dw[t >> 6];
-    BatchState& S = W.st;
-    lbk_search& s = W.s;
-    for (int p = blockIdx.x; p < a.B; p += gridDim.x) {
-        const BatchView V = batch_view(a, p);
-        double* const d = V.d();
-        const double* const Ap = dq.A + (int64_t)p * dq.astride;
-        const double* const bp = dq.b + (int64_t)p * dq.ldb;
-        double* const tv = dq.xbase + (int64_t)p * 2 * a.vstride;
-        double* const gt = tv + a.vstride;
-        // lbk_dense_eval: the rows at z with the gradient into gout, then f (and gout . gout) from the terms
-        auto eval = [&](const double* z, double* gout, double (&t2)[2]) {
-            dense_rows(Ap, bp, z, gout, tv, n, dq.lda);
-            batch_pass<2>(OpTermsDot<false>{tv, gout}, geo, L, t2);
-            S.vecs += (double)n + 5.0;
-        };
-        if (batch_enter(a, V, p, n, S)) continue;
-        if (a.init) {  // f, g and g.g at x0
-            double t2[2];
-            eval(V.vec(0), V.vec(1), t2);
-            S.f_cur = t2[0];
-            S.gg = t2[1];
-        }
-
-        for (int it = 0; it < a.iters; ++it) {
-            BatchIter I;
-            if (batch_iter_top(a, V, S, I)) break;
-            batch_direction(V, I, geo, L, S, W);
-
-            // ---- d into its buffer, g . d that pass's total; a direction that is no descent
-            // direction gives way to -g, materialised again (once) ----
-            double gd;
-            for (bool fell_back = false;;) {
-                gd = batch_materialise_d(V, I, geo, L, S, W);
-                if (!(gd >= 0) || fell_back) break;
-                S.ev[0]++;
-                W.dmode = LBK_D_NEG_G;
-                fell_back = true;
-            }
-            D.hz_valid = D.hf_valid = D.gt_valid = 0;  // host_invalidate: nothing cached refers to this x, d
-
-            auto point = [&](double alpha) {  // host_point_issue
-                if (D.hz_valid && D.hz_alpha == alpha) return;
-                dense_point(I.xn, I.x, d, alpha, n);
-                S.vecs += 3.0;
-                D.hz_valid = 1;
-                D.hz_alpha = alpha;
-                D.hf_valid = 0;
-            };
-            // one evaluation at z(alpha) with the gradient into dst: f is cached with it, and the
-            // gradient when dst is gt (host_g_at's dense branch; host_f_at's is this with dst = gt)
-            auto eval_at = [&](double alpha, double* dst) {
-                point(alpha);
-                double t2[2];
-                eval(I.xn, dst, t2);
-                D.hf_valid = 1;
-                D.hf_alpha = alpha;
-                D.hf_val = t2[0];
-                if (dst == gt) {
-                    D.gt_valid = 1;
-                    D.gt_alpha = alpha;
-                } else if (D.gt_valid && D.gt_alpha == alpha) {
-                    D.gt_valid = 0;
-                }
-            };
-            auto f_at = [&](double alpha) -> double {  // host_f_at
-                if (!(D.hf_valid && D.hf_alpha == alpha && D.hz_valid && D.hz_alpha == alpha)) eval_at(alpha, gt);
-                return D.hf_val;
-            };
-            auto g_at = [&](double alpha, double* dst) {  // host_g_at
-                if (D.gt_valid && D.gt_alpha == alpha) {
-                    if (dst != gt) {
-                        for (int64_t i = t; i < n; i += LB_BLOCK) dst[i] = gt[i];
-                        batch_stage_sync();
-                        S.vecs += 2.0;
-                    }
-                    return;
-                }
-                eval_at(alpha, dst);
-            };
-
-            // ---- the line search, from the top, nothing cached (no first trial rode a commit) ----
-            batch_search_begin(a, S, s, gd);
-            W.capped = W.passes = 0;
-            // lbfgs_driver.c trial() for an external objective: one step per call, f from its cache or
-            // an evaluation, with need_g the gradient in gt and gt . d; the backtracking-Wolfe search
-            // asks for the gradient before f (line_search.cpp:39-42)
-            auto trial = [&](double alpha, bool need_g, double& f, double& dphi) -> bool {
-                if (LS == 3 && W.passes >= LBK_BATCH_BTW_CAP) {  // the reference's loop has no bound of its own
-                    W.capped = 1;
-                    return false;
-                }
-                W.passes++;
-                const bool g_first = need_g && LS == 3;
-                // (a loop of two steps, not unrolled, so that f_at and g_at are inlined once each)
-#pragma unroll 1
-                for (int step = 0; step < 2; ++step) {
-                    if ((step == 0) == g_first) {
-                        if (need_g) g_at(alpha, gt);
-                    } else {
-                        f = f_at(alpha);
-                    }
-                }
-                if (need_g) {
-                    double t1[1];
-                    batch_pass<1>(OpDot<false>{gt, d}, geo, L, t1);
-                    S.vecs += 2.0;
-                    dphi = t1[0];
-                    S.trials_fg++;
-                } else {
-                    S.trials_f++;
-                }
-                return true;
-            };
-            search_loop<LS>(s, trial);
-            if (W.capped || !s.done) {
-                S.status = LBFGS_ERR_STATE;
-                break;
-            }
-            const double alpha = s.step;
-            batch_trace_step(a, V, S, alpha);
-
-            // ---- commit (lbfgs_driver.c commit(), ext_obj): f at the step, then - unless the step
-            // failed - the gradient at the step into gn, and the commit pass that reads it ----
-            const double f_new = f_at(alpha);
-            S.f_cur = f_new;
-            if (alpha < 1e-10) {
-                S.status = LBFGS_STATUS_LS_FAILED;
-                break;
-            }
-            g_at(alpha, I.gn);
-            batch_pass<7>(OpCommit<LBK_OBJ_NONE, LBK_D_BUF, false, false>{I.x, batch_buf_args(V, I), alpha, I.xn, I.gn,
-                                                                          I.so, I.yo, n, n, 0.0},
-                          geo, L, W.tot);
-            W.tot[LBK_C_F] = f_new;
-            S.vecs += 7.0;
-            S.commits++;
-            batch_accept(a.m, S, W);
-        }
-        batch_leave(a, V, p, n, S);
-    }
+__global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense(BatchArgs a, BatchDenseArgs dq, Geo geo_b) {
+    constexpr bool RAGGED = false;
+    const BatchRagged rg = {nullptr, nullptr};
+#include "lbfgs_kernels_batch_solve_dense.h"
 }
 
-typedef void (*batch_dense_kernel_t)(BatchArgs, BatchDenseArgs, Geo);
-batch_dense_kernel_t batch_dense_kernel(int ls) {
+template <int LS>
+__global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense_ragged(BatchArgs a, BatchDenseArgs dq, Geo geo_b,
+                                                                       BatchRagged rg) {
+    constexpr bool RAGGED = true;
+#include "lbfgs_kernels_batch_solve_dense.h"
+}
+
+// A ragged batch has its own kernels, with the BatchRagged as their last argument; a uniform batch
+// runs the kernels it always ran.
+const void* batch_dense_kernel(int ls, bool ragged) {
     switch (ls) {
-        case 0: return k_batch_solve_dense<0>;
-        case 1: return k_batch_solve_dense<1>;
-        case 2: return k_batch_solve_dense<2>;
-        default: return k_batch_solve_dense<3>;
+        case 0: return ragged ? (const void*)k_batch_solve_dense_ragged<0> : (const void*)k_batch_solve_dense<0>;
+        case 1: return ragged ? (const void*)k_batch_solve_dense_ragged<1> : (const void*)k_batch_solve_dense<1>;
+        case 2: return ragged ? (const void*)k_batch_solve_dense_ragged<2> : (const void*)k_batch_solve_dense<2>;
+        default: return ragged ? (const void*)k_batch_solve_dense_ragged<3> : (const void*)k_batch_solve_dense<3>;
     }
 }
 
-typedef void (*batch_kernel_t)(BatchArgs, Geo);
 template <int OBJ>
-batch_kernel_t batch_kernel_ls(int ls) {
+const void* batch_kernel_ls(int ls, bool ragged) {
     switch (ls) {
-        case 0: return k_batch_solve<OBJ, 0>;
-        case 1: return k_batch_solve<OBJ, 1>;
-        case 2: return k_batch_solve<OBJ, 2>;
-        default: return k_batch_solve<OBJ, 3>;
+        case 0: return ragged ? (const void*)k_batch_solve_ragged<OBJ, 0> : (const void*)k_batch_solve<OBJ, 0>;
+        case 1: return ragged ? (const void*)k_batch_solve_ragged<OBJ, 1> : (const void*)k_batch_solve<OBJ, 1>;
+        case 2: return ragged ? (const void*)k_batch_solve_ragged<OBJ, 2> : (const void*)k_batch_solve<OBJ, 2>;
+        default: return ragged ? (const void*)k_batch_solve_ragged<OBJ, 3> : (const void*)k_batch_solve<OBJ, 3>;
     }
 }
-batch_kernel_t batch_kernel(int obj, int ls) {
+const void* batch_kernel(int obj, int ls, bool ragged) {
     switch (obj) {
-        case LBK_OBJ_ROSENBROCK: return batch_kernel_ls<LBK_OBJ_ROSENBROCK>(ls);
-        case LBK_OBJ_QUAD_TRIDIAG: return batch_kernel_ls<LBK_OBJ_QUAD_TRIDIAG>(ls);
-        default: return batch_kernel_ls<LBK_OBJ_QUAD_SEPARABLE>(ls);
+        case LBK_OBJ_ROSENBROCK: return batch_kernel_ls<LBK_OBJ_ROSENBROCK>(ls, ragged);
+        case LBK_OBJ_QUAD_TRIDIAG: return batch_kernel_ls<LBK_OBJ_QUAD_TRIDIAG>(ls, ragged);
+        default: return batch_kernel_ls<LBK_OBJ_QUAD_SEPARABLE>(ls, ragged);
     }
 }
 
@@ -759,11 +580,17 @@ int64_t batch_vstride(int64_t n) { return LBK_FRONT + ((n + 511) / 512) * 512 + 
 }  // namespace
 
 struct lbfgs_batch {
-    int64_t n, vstride, pstride;
+    int64_t n, vstride, pstride;  // a ragged batch: n = the largest n_p, vstride and pstride unused
+    // a ragged batch (lbfgs_batch_create_ragged): the sizes, and the B + 1 running sums of n_p, of
+    // n_p * n_p and of the vector strides; the table and the order of work in device memory
+    bool ragged;
+    std::vector<int64_t> np, off, off2, vsum;
+    BatchRow* tab;
+    int* order;
     int m, B, device, cus;
     int max_wg, iters;
     double* vecs;     // B problems x NVEC vectors, each laid out as lbk_vec_alloc's
-    double* xio;      // [B][n]
+    double* xio;      // [B][n]; a ragged batch: packed, problem p at off[p]
     BatchState* st;
     int* running;
     double* tr;       // device trace, [B][3][tr_cap]
@@ -799,10 +626,12 @@ struct lbfgs_batch {
         }                                                                                       \
     } while (0)
 
+static int64_t batch_sum_v(const lbfgs_batch* b);
+
 // The per-problem terms vector t and trial gradient gt of the dense objective, allocated once.
 static int batch_dense_scratch(lbfgs_batch* b, const char* who) {
     if (b->dq_x) return 0;
-    const size_t xbytes = sizeof(double) * 2 * (size_t)b->vstride * (size_t)b->B;
+    const size_t xbytes = sizeof(double) * 2 * (size_t)batch_sum_v(b);
     if (hipMalloc((void**)&b->dq_x, xbytes) != hipSuccess) {  // the batch stays usable for the stencil objectives
         (void)hipGetLastError();
         b->dq_x = nullptr;
@@ -850,7 +679,56 @@ static bool batch_overlap(const double* p, int64_t np, const double* q, int64_t 
     return (uintptr_t)p < (uintptr_t)(q + nq) && (uintptr_t)q < (uintptr_t)(p + np);
 }
 
+// ---- the sizes a ragged batch's checks and copies need; a uniform batch answers with n ----
+static int64_t batch_np(const lbfgs_batch* b, int64_t p) { return b->ragged ? b->np[(size_t)p] : b->n; }
+static int64_t batch_sum_n(const lbfgs_batch* b) { return b->ragged ? b->off[(size_t)b->B] : b->n * b->B; }
+static int64_t batch_sum_v(const lbfgs_batch* b) { return b->ragged ? b->vsum[(size_t)b->B] : b->vstride * b->B; }
+// the doubles a batch of rows spans: (B - 1) * ld + n_{B-1} (ld 0: one row), or packed the sum of n_p
+static int64_t batch_xspan(const lbfgs_batch* b, int64_t ld) {
+    if (ld == LBFGS_BATCH_PACKED) return batch_sum_n(b);
+    return batch_span(b->B, ld, batch_np(b, b->B - 1));
+}
+// ... and the matrices: (B - 1) * astride + (n_{B-1} - 1) * lda + n_{B-1}, or packed the sum of n_p * n_p
+static int64_t batch_aspan(const lbfgs_batch* b, int64_t astride, int64_t lda) {
+    if (astride == LBFGS_BATCH_PACKED) return b->off2[(size_t)b->B];
+    const int64_t nl = batch_np(b, b->B - 1);
+    return batch_span(b->B, astride, (nl - 1) * lda + nl);
+}
+static bool batch_any_over(const lbfgs_batch* b, int64_t limit) {
+    if (!b->ragged) return b->n > limit;
+    for (int64_t v : b->np)
+        if (v > limit) return true;
+    return false;
+}
+
+// The order of work of a ragged batch: the largest problems first (ties by index), so that with
+// fewer workgroups than problems no workgroup is left with a large problem at the end. A launch
+// with a workgroup for every problem does not use it (batch_solve). Results do not depend on it;
+// LBFGS_BATCH_ORDER=identity gives 0, 1, 2, ... (tests and measurements).
+static void batch_order(const std::vector<int64_t>& np, std::vector<int>& order) {
+    order.resize(np.size());
+    for (size_t i = 0; i < np.size(); ++i) order[i] = (int)i;
+    const char* e = getenv("LBFGS_BATCH_ORDER");
+    if (e && strcmp(e, "identity") == 0) return;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return np[(size_t)x] > np[(size_t)y]; });
+}
+
 extern "C" {
+
+int lbfgs_batch_ragged_plan(const int64_t* n, int batch, int m, int dense, double* bytes) {
+    if (!n || batch < 1 || m < 1 || m > LBK_SMALL_HMAX) return LBFGS_ERR_BAD_ARG;
+    double total = 0.0;
+    for (int p = 0; p < batch; ++p) {
+        if (n[p] < 1 || n[p] > (dense ? LBK_BATCH_DENSE_NMAX : LBK_BATCH_NMAX)) return LBFGS_ERR_BAD_ARG;
+        const double np = (double)n[p], vs = (double)batch_vstride(n[p]);
+        // the problem as a batch of one (lbfgs_batch_plan), its row of the table and its entry of the order
+        total += 8.0 * ((double)LBK_BATCH_NVEC(m) * vs + np) + (double)sizeof(BatchState) +
+                 (double)(sizeof(BatchRow) + sizeof(int));
+        if (dense) total += 8.0 * (2.0 * vs + np) + 8.0 * np * np;  // t and gt, b, the matrix
+    }
+    if (bytes) *bytes = total;
+    return 0;
+}
 
 int lbfgs_batch_plan(int64_t n, int m, int batch, double* bytes) {
     if (n < 1 || n > LBK_BATCH_NMAX || m < 1 || m > LBK_SMALL_HMAX || batch < 1) return LBFGS_ERR_BAD_ARG;
@@ -881,14 +759,16 @@ void lbfgs_batch_destroy(lbfgs_batch* b) {
     if (b->dq_A) (void)hipFree(b->dq_A);
     if (b->dq_b) (void)hipFree(b->dq_b);
     if (b->dq_x) (void)hipFree(b->dq_x);
+    if (b->tab) (void)hipFree(b->tab);
+    if (b->order) (void)hipFree(b->order);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
 
-int lbfgs_batch_create(lbfgs_batch** out, int64_t n, int m, int batch, int device) {
-    if (!out) return LBFGS_ERR_BAD_ARG;
-    *out = nullptr;
-    if (lbfgs_batch_plan(n, m, batch, nullptr) != 0) return LBFGS_ERR_BAD_ARG;
+}  // extern "C"
+
+// both creators: n the size (a ragged batch: the largest), sizes the n_p of a ragged batch or null
+static int batch_create(lbfgs_batch** out, int64_t n, const int64_t* sizes, int m, int batch, int device) {
     lbk_geo G;
     if (lbk_geometry_plan(n, 0, 1, &G) != 0 || G.L != 512 || G.nseg > LBK_BATCH_SEGMAX) return LBFGS_ERR_BAD_ARG;
     lbfgs_batch* b = new (std::nothrow) lbfgs_batch();
@@ -899,6 +779,25 @@ int lbfgs_batch_create(lbfgs_batch** out, int64_t n, int m, int batch, int devic
     b->device = device;
     b->vstride = batch_vstride(n);
     b->pstride = b->vstride * LBK_BATCH_NVEC(m);
+    std::vector<BatchRow> rows;
+    std::vector<int> order;
+    if (sizes) {
+        b->ragged = true;
+        b->np.assign(sizes, sizes + batch);
+        b->off.assign((size_t)batch + 1, 0);
+        b->off2.assign((size_t)batch + 1, 0);
+        b->vsum.assign((size_t)batch + 1, 0);
+        rows.resize((size_t)batch);
+        for (int p = 0; p < batch; ++p) {
+            const int64_t np = sizes[p], vs = batch_vstride(np);
+            rows[(size_t)p] = {np, b->vsum[(size_t)p] * LBK_BATCH_NVEC(m), vs, b->off[(size_t)p], b->off2[(size_t)p],
+                               b->vsum[(size_t)p] * 2};
+            b->off[(size_t)p + 1] = b->off[(size_t)p] + np;
+            b->off2[(size_t)p + 1] = b->off2[(size_t)p] + np * np;
+            b->vsum[(size_t)p + 1] = b->vsum[(size_t)p] + vs;
+        }
+        batch_order(b->np, order);
+    }
     b->geo.n = n;
     b->geo.L = G.L;
     b->geo.nseg = G.nseg;
@@ -912,16 +811,23 @@ int lbfgs_batch_create(lbfgs_batch** out, int64_t n, int m, int batch, int devic
     b->geo.ppart = nullptr;
     b->geo.edge_slot = nullptr;
     hipDeviceProp_t prop;
-    const size_t vbytes = sizeof(double) * (size_t)b->pstride * (size_t)batch;
+    const size_t vbytes = sizeof(double) * (size_t)LBK_BATCH_NVEC(m) * (size_t)batch_sum_v(b);
     if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess ||
         hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
         hipMalloc((void**)&b->vecs, vbytes) != hipSuccess ||
-        hipMalloc((void**)&b->xio, sizeof(double) * (size_t)n * (size_t)batch) != hipSuccess ||
+        hipMalloc((void**)&b->xio, sizeof(double) * (size_t)batch_sum_n(b)) != hipSuccess ||
         hipMalloc((void**)&b->st, sizeof(BatchState) * (size_t)batch) != hipSuccess ||
         hipMalloc((void**)&b->running, sizeof(int)) != hipSuccess ||
         // ghost cells and padding are zero and stay zero: no pass stores outside [0, n)
         hipMemsetAsync(b->vecs, 0, vbytes, b->stream) != hipSuccess ||
         hipMemsetAsync(b->st, 0, sizeof(BatchState) * (size_t)batch, b->stream) != hipSuccess ||
+        // the table and the order of work, written once
+        (sizes && (hipMalloc((void**)&b->tab, sizeof(BatchRow) * (size_t)batch) != hipSuccess ||
+                   hipMalloc((void**)&b->order, sizeof(int) * (size_t)batch) != hipSuccess ||
+                   hipMemcpyAsync(b->tab, rows.data(), sizeof(BatchRow) * (size_t)batch, hipMemcpyHostToDevice,
+                                  b->stream) != hipSuccess ||
+                   hipMemcpyAsync(b->order, order.data(), sizeof(int) * (size_t)batch, hipMemcpyHostToDevice,
+                                  b->stream) != hipSuccess)) ||
         hipStreamSynchronize(b->stream) != hipSuccess) {
         (void)hipGetLastError();
         lbfgs_batch_destroy(b);
@@ -929,6 +835,32 @@ int lbfgs_batch_create(lbfgs_batch** out, int64_t n, int m, int batch, int devic
     }
     b->cus = prop.multiProcessorCount;
     *out = b;
+    return 0;
+}
+
+extern "C" {
+
+int lbfgs_batch_create(lbfgs_batch** out, int64_t n, int m, int batch, int device) {
+    if (!out) return LBFGS_ERR_BAD_ARG;
+    *out = nullptr;
+    if (lbfgs_batch_plan(n, m, batch, nullptr) != 0) return LBFGS_ERR_BAD_ARG;
+    return batch_create(out, n, nullptr, m, batch, device);
+}
+
+int lbfgs_batch_create_ragged(lbfgs_batch** out, const int64_t* n, int m, int batch, int device) {
+    if (!out) return LBFGS_ERR_BAD_ARG;
+    *out = nullptr;
+    if (lbfgs_batch_ragged_plan(n, batch, m, 0, nullptr) != 0) return LBFGS_ERR_BAD_ARG;
+    return batch_create(out, *std::max_element(n, n + batch), n, m, batch, device);
+}
+
+int lbfgs_batch_sizes(const lbfgs_batch* b, int64_t* n_out, int64_t* offset_out) {
+    if (!b) return LBFGS_ERR_BAD_ARG;
+    for (int64_t p = 0; p < b->B; ++p) {
+        if (n_out) n_out[p] = batch_np(b, p);
+        if (offset_out) offset_out[p] = b->ragged ? b->off[(size_t)p] : p * b->n;
+    }
+    if (offset_out) offset_out[b->B] = batch_sum_n(b);
     return 0;
 }
 
@@ -944,19 +876,25 @@ int lbfgs_batch_set_launch(lbfgs_batch* b, int max_workgroups, int iters_per_lau
 int lbfgs_batch_set_dense_quadratics(lbfgs_batch* b, const double* A, int shared_A, const double* bvec) {
     if (!b) return LBFGS_ERR_BAD_ARG;
     b->err[0] = 0;
-    if (!A || !bvec || b->n > LBK_BATCH_DENSE_NMAX) {
+    if (!A || !bvec || batch_any_over(b, LBK_BATCH_DENSE_NMAX)) {
         snprintf(b->err, sizeof b->err, "lbfgs_batch_set_dense_quadratics: A and b, and a batch of n <= %d",
                  LBK_BATCH_DENSE_NMAX);
         return LBFGS_ERR_BAD_ARG;
     }
+    if (b->ragged && shared_A) {
+        snprintf(b->err, sizeof b->err, "lbfgs_batch_set_dense_quadratics: one shared A needs problems of one size, "
+                 "not a ragged batch");
+        return LBFGS_ERR_BAD_ARG;
+    }
     BHIP(b, hipSetDevice(b->device));
     const size_t nn = (size_t)b->n * (size_t)b->n, B = (size_t)b->B;
-    const size_t a_doubles = shared_A ? nn : nn * B;
+    const size_t a_doubles = b->ragged ? (size_t)b->off2[B] : shared_A ? nn : nn * B;
+    const size_t b_doubles = (size_t)batch_sum_n(b);
     b->dq_set = false;
     b->dq_ref = false;  // a caller's buffers are referenced no longer
     b->ref_A = b->ref_b = nullptr;
     bool ok = true;
-    if (!b->dq_b) ok = hipMalloc((void**)&b->dq_b, sizeof(double) * (size_t)b->n * B) == hipSuccess;
+    if (!b->dq_b) ok = hipMalloc((void**)&b->dq_b, sizeof(double) * b_doubles) == hipSuccess;
     if (ok) {
         const int rc = batch_dense_scratch(b, "lbfgs_batch_set_dense_quadratics");
         if (rc != 0) return rc;
@@ -974,7 +912,7 @@ int lbfgs_batch_set_dense_quadratics(lbfgs_batch* b, const double* A, int shared
         return LBFGS_ERR_NOMEM;
     }
     BHIP(b, hipMemcpyAsync(b->dq_A, A, sizeof(double) * a_doubles, hipMemcpyHostToDevice, b->stream));
-    BHIP(b, hipMemcpyAsync(b->dq_b, bvec, sizeof(double) * (size_t)b->n * B, hipMemcpyHostToDevice, b->stream));
+    BHIP(b, hipMemcpyAsync(b->dq_b, bvec, sizeof(double) * b_doubles, hipMemcpyHostToDevice, b->stream));
     BHIP(b, hipStreamSynchronize(b->stream));
     b->dq_shared = shared_A != 0;
     b->dq_set = true;
@@ -985,22 +923,28 @@ int lbfgs_batch_set_dense_quadratics_device(lbfgs_batch* b, const double* A_dev,
                                             const double* b_dev, int64_t ldb) {
     if (!b) return LBFGS_ERR_BAD_ARG;
     b->err[0] = 0;
-    const int64_t n = b->n, B = b->B;
+    const int64_t n = b->n;  // a ragged batch: the largest n_p
     const char* bad = nullptr;
-    if (n > LBK_BATCH_DENSE_NMAX)
+    const bool a_packed = a_batch_stride == LBFGS_BATCH_PACKED || lda == LBFGS_BATCH_PACKED;
+    if (batch_any_over(b, LBK_BATCH_DENSE_NMAX))
         bad = "a batch of n <= 4096";
     else if (!A_dev || !b_dev)
         bad = "A_dev and b_dev";
-    else if (lda < n)
+    else if (!b->ragged && (a_packed || ldb == LBFGS_BATCH_PACKED))
+        bad = "LBFGS_BATCH_PACKED is a stride of ragged batches only";
+    else if (a_packed && !(a_batch_stride == LBFGS_BATCH_PACKED && lda == LBFGS_BATCH_PACKED))
+        bad = "a_batch_stride and lda both strides or both LBFGS_BATCH_PACKED";
+    else if (b->ragged && ((!a_packed && a_batch_stride == 0) || ldb == 0))
+        bad = "a ragged batch has no shared A or b: a_batch_stride and ldb not 0";
+    else if (!a_packed && lda < n)
         bad = "lda >= n";
-    else if (a_batch_stride != 0 && a_batch_stride < (n - 1) * lda + n)
+    else if (!a_packed && a_batch_stride != 0 && a_batch_stride < (n - 1) * lda + n)
         bad = "a_batch_stride >= (n - 1) * lda + n, or 0 for one shared matrix";
-    else if (ldb != 0 && ldb < n)
-        bad = "ldb >= n, or 0 for one shared b";
+    if (!bad && ldb != LBFGS_BATCH_PACKED && ldb != 0 && ldb < n) bad = "ldb >= n, or 0 for one shared b";
     if (!bad) {
         BHIP(b, hipSetDevice(b->device));
-        if (!batch_caller_range(b, A_dev, batch_span(B, a_batch_stride, (n - 1) * lda + n)) ||
-            !batch_caller_range(b, b_dev, batch_span(B, ldb, n)))
+        if (!batch_caller_range(b, A_dev, batch_aspan(b, a_batch_stride, lda)) ||
+            !batch_caller_range(b, b_dev, batch_xspan(b, ldb)))
             bad = "A_dev and b_dev 8-byte aligned in device memory of the batch's device (not pinned host, not managed)";
     }
     if (bad) {  // the data set before, if any, stay as they are
@@ -1086,12 +1030,14 @@ static int batch_solve(lbfgs_batch* b, const char* who, int objective, int line_
         dq.astride = b->dq_ref ? b->ref_astride : b->dq_shared ? 0 : b->n * b->n;
         dq.lda = b->dq_ref ? b->ref_lda : b->n;
         dq.ldb = b->dq_ref ? b->ref_ldb : b->n;
+        if (b->ragged && !b->dq_ref) dq.astride = dq.lda = dq.ldb = LBFGS_BATCH_PACKED;  // the batch's own copies
     }
+    BatchRagged rg = {b->tab, nullptr};
     // the one kernel of this solve and its arguments
-    const void* const kern = dense ? (const void*)batch_dense_kernel(line_search)
-                                   : (const void*)batch_kernel(objective, line_search);
-    void* args_stencil[] = {&a, &b->geo};
-    void* args_dense[] = {&a, &dq, &b->geo};
+    const void* const kern = dense ? batch_dense_kernel(line_search, b->ragged)
+                                   : batch_kernel(objective, line_search, b->ragged);
+    void* args_stencil[] = {&a, &b->geo, &rg};     // rg: the ragged kernels' last argument; a uniform batch's
+    void* args_dense[] = {&a, &dq, &b->geo, &rg};  // kernels have none, and the entry is not read
     void** const kargs = dense ? args_dense : args_stencil;
     int grid = b->max_wg;
     if (grid <= 0) {  // every workgroup resident: occupancy x CUs
@@ -1100,10 +1046,13 @@ static int batch_solve(lbfgs_batch* b, const char* who, int objective, int line_
         grid = std::max(1, per_cu) * std::max(1, b->cus);
     }
     grid = std::min(grid, b->B);
+    // the order of work balances workgroups that take several problems each; with one problem each
+    // there is nothing to balance, and the problems stay where their index puts them
+    if (grid < b->B) rg.order = b->order;
     auto launch = [&] { return hipLaunchKernel(kern, dim3(grid), dim3(LB_BLOCK), kargs, 0, b->stream); };
     // x0 up (one contiguous copy; each workgroup moves its problem's x0 into the vector layout)
     if (x0_host)
-        BHIP(b, hipMemcpyAsync(b->xio, x0_host, sizeof(double) * (size_t)b->n * (size_t)b->B, hipMemcpyHostToDevice,
+        BHIP(b, hipMemcpyAsync(b->xio, x0_host, sizeof(double) * (size_t)batch_sum_n(b), hipMemcpyHostToDevice,
                                b->stream));
     // every launch takes each unfinished problem at least one iteration further, or ends it
     const long long max_launches = (long long)max_iterations / a.iters + 2;
@@ -1125,7 +1074,7 @@ static int batch_solve(lbfgs_batch* b, const char* who, int objective, int line_
     b->hst.resize((size_t)b->B);
     BHIP(b, hipMemcpyAsync(b->hst.data(), b->st, sizeof(BatchState) * (size_t)b->B, hipMemcpyDeviceToHost, b->stream));
     if (x_out_host)
-        BHIP(b, hipMemcpyAsync(x_out_host, b->xio, sizeof(double) * (size_t)b->n * (size_t)b->B, hipMemcpyDeviceToHost,
+        BHIP(b, hipMemcpyAsync(x_out_host, b->xio, sizeof(double) * (size_t)batch_sum_n(b), hipMemcpyDeviceToHost,
                                b->stream));
     b->htr_cap = 0;
     if (trace) {
@@ -1149,7 +1098,7 @@ static int batch_solve(lbfgs_batch* b, const char* who, int objective, int line_
             r.trials_fg = s.trials_fg;
             r.commits = s.commits;
             r.passes = launches;
-            r.bytes = s.vecs * 8.0 * (double)b->n;
+            r.bytes = s.vecs * 8.0 * (double)batch_np(b, p);
             r.seconds = secs;
             r.h_min = s.h_min;
             r.h_max = s.h_min < 0 ? -1 : s.h_max;
@@ -1168,7 +1117,8 @@ int lbfgs_batch_minimize(lbfgs_batch* b, int objective, int line_search, const l
         snprintf(b->err, sizeof b->err, "lbfgs_batch_minimize: x0_host");
         return LBFGS_ERR_BAD_ARG;
     }
-    return batch_solve(b, "lbfgs_batch_minimize", objective, line_search, k, b->xio, b->n, b->xio, b->n, x0_host,
+    const int64_t ld = b->ragged ? LBFGS_BATCH_PACKED : b->n;  // the batch's own rows
+    return batch_solve(b, "lbfgs_batch_minimize", objective, line_search, k, b->xio, ld, b->xio, ld, x0_host,
                        x_out_host, max_iterations, tolerance, flags, out);
 }
 
@@ -1177,15 +1127,20 @@ int lbfgs_batch_minimize_device(lbfgs_batch* b, int objective, int line_search, 
                                 double tolerance, unsigned flags, lbfgs_result* out) {
     if (!b) return LBFGS_ERR_BAD_ARG;
     b->err[0] = 0;
-    const int64_t n = b->n, B = b->B;
+    const int64_t n = b->n;  // a ragged batch: the largest n_p
     const char* bad = nullptr;
+    const bool packed0 = ldx0 == LBFGS_BATCH_PACKED, packed = x_out_dev && ldx == LBFGS_BATCH_PACKED;
     if (!x0_dev)
         bad = "x0_dev";
-    else if (ldx0 != 0 && ldx0 < n)
+    else if (!b->ragged && (packed0 || packed))
+        bad = "LBFGS_BATCH_PACKED is a stride of ragged batches only";
+    else if (b->ragged && ldx0 == 0)
+        bad = "a ragged batch has no x0 shared by every problem: ldx0 >= the largest n, or LBFGS_BATCH_PACKED";
+    else if (!packed0 && ldx0 != 0 && ldx0 < n)
         bad = "ldx0 >= n, or 0 for one x0 shared by every problem";
-    else if (x_out_dev && ldx < n)
+    else if (x_out_dev && !packed && ldx < n)
         bad = "ldx >= n";
-    const int64_t span0 = batch_span(B, ldx0, n), span = batch_span(B, ldx, n);
+    const int64_t span0 = bad ? 0 : batch_xspan(b, ldx0), span = bad || !x_out_dev ? 0 : batch_xspan(b, ldx);
     if (!bad) {
         BHIP(b, hipSetDevice(b->device));
         if (!batch_caller_range(b, x0_dev, span0) || (x_out_dev && !batch_caller_range(b, x_out_dev, span)))
@@ -1199,8 +1154,8 @@ int lbfgs_batch_minimize_device(lbfgs_batch* b, int objective, int line_search, 
         if (!in_place && batch_overlap(x_out_dev, span, x0_dev, span0))
             bad = "x_out_dev either x0_dev itself with ldx == ldx0 >= n or not overlapping it";
         else if (b->dq_set && b->dq_ref &&
-                 (batch_overlap(x_out_dev, span, b->ref_A, batch_span(B, b->ref_astride, (n - 1) * b->ref_lda + n)) ||
-                  batch_overlap(x_out_dev, span, b->ref_b, batch_span(B, b->ref_ldb, n))))
+                 (batch_overlap(x_out_dev, span, b->ref_A, batch_aspan(b, b->ref_astride, b->ref_lda)) ||
+                  batch_overlap(x_out_dev, span, b->ref_b, batch_xspan(b, b->ref_ldb))))
             bad = "x_out_dev not overlapping the A and b set by lbfgs_batch_set_dense_quadratics_device";
     }
     if (bad) {
@@ -1209,7 +1164,8 @@ int lbfgs_batch_minimize_device(lbfgs_batch* b, int objective, int line_search, 
     }
     // without x_out_dev the kernel's x goes to the batch's own rows
     return batch_solve(b, "lbfgs_batch_minimize_device", objective, line_search, k, x0_dev, ldx0,
-                       x_out_dev ? x_out_dev : b->xio, x_out_dev ? ldx : n, nullptr, nullptr, max_iterations, tolerance,
+                       x_out_dev ? x_out_dev : b->xio, x_out_dev ? ldx : b->ragged ? LBFGS_BATCH_PACKED : n, nullptr,
+                       nullptr, max_iterations, tolerance,
                        flags, out);
 }
 

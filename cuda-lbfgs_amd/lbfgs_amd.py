@@ -170,6 +170,9 @@ def lib():
     L.lbfgs_batch_minimize_device.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Constants), vp, C.c_int64, vp, C.c_int64,
                                               C.c_int, C.c_double, C.c_uint, C.POINTER(Result)]
     L.lbfgs_batch_set_dense_quadratics_device.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64]
+    L.lbfgs_batch_ragged_plan.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.lbfgs_batch_create_ragged.argtypes = [C.POINTER(vp), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int]
+    L.lbfgs_batch_sizes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.lbfgs_set_device_objective.argtypes = [vp, C.POINTER(DeviceFn)]
     L.lbfgs_minimize_device.argtypes = [vp, C.c_int, C.POINTER(HostFn), C.c_int, C.POINTER(Constants),
                                         vp, vp, C.c_int, C.c_double, C.c_uint, C.POINTER(Result)]
@@ -200,6 +203,7 @@ EXPORTED_SYMBOLS = [
     "lbfgs_batch_set_launch", "lbfgs_batch_minimize", "lbfgs_batch_trace_len", "lbfgs_batch_trace_get",
     "lbfgs_batch_events_get", "lbfgs_batch_dense_plan", "lbfgs_batch_set_dense_quadratics",
     "lbfgs_batch_minimize_device", "lbfgs_batch_set_dense_quadratics_device",
+    "lbfgs_batch_ragged_plan", "lbfgs_batch_create_ragged", "lbfgs_batch_sizes",
     "lbfgs_set_device_objective", "lbfgs_minimize_device", "lbfgs_solver_init_device", "lbfgs_get_x_device",
     "lbfgs_reducer_create", "lbfgs_reducer_destroy", "lbfgs_reducer_dot",
 ]
@@ -323,6 +327,30 @@ def plan_dense(n, m, batch, shared=False):
     return b.value
 
 
+BATCH_PACKED = -1  # LBFGS_BATCH_PACKED: the stride of a ragged batch's packed rows
+
+
+def _sizes_array(sizes):
+    a = np.asarray(list(sizes))
+    if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iu":
+        raise ValueError(f"a ragged batch's sizes: a non-empty sequence of integers is required, got {sizes!r}")
+    return (C.c_int64 * a.size)(*[int(v) for v in a])
+
+
+def plan_ragged(sizes, m, dense=False):
+    """Device bytes a ragged Batch(sizes, m) would take (no device needed), with dense its t, gt, b and
+    packed matrices included; raises LbfgsError outside the limits (lbfgs_batch_ragged_plan)."""
+    arr = _sizes_array(sizes)
+    b = C.c_double()
+    rc = lib().lbfgs_batch_ragged_plan(arr, len(arr), int(m), int(bool(dense)), C.byref(b))
+    if rc != 0:
+        e = LbfgsError(f"lbfgs_batch_ragged_plan failed ({rc}): 1 <= n_p <= {DENSE_BATCH_NMAX if dense else 32768} "
+                       "for every problem, 1 <= m <= 16")
+        e.rc = rc
+        raise e
+    return b.value
+
+
 class Batch:
     """`batch` independent small problems (same n, m, objective, line search, constants, tolerance
     and iteration limit; their own x0, and for objective "dense" their own A and b, see
@@ -331,18 +359,41 @@ class Batch:
 
         with L.Batch(n=10_000, m=5, batch=256) as b:
             res = b.minimize("rosenbrock", X0, "backtracking", max_iterations=100)   # X0: 256 x n
+
+    A sequence of sizes for `n` makes a RAGGED batch, problem p of size n[p] (batch = len(n)): .ragged,
+    .sizes, .offsets (batch + 1 packed offsets) and .n, the largest size. Its host arrays are lists of
+    per-problem arrays or one packed array; its device tensors padded rows or one packed tensor.
+
+        with L.Batch(n=[513, 5, 1537], m=5) as b:
+            res = b.minimize("rosenbrock", [x0_a, x0_b, x0_c])                      # res["x"]: 3 arrays
     """
 
-    def __init__(self, n, m, batch, device=0):
-        self.n, self.m, self.batch, self.device = int(n), int(m), int(batch), int(device)
+    def __init__(self, n, m, batch=None, device=0):
+        self.m, self.device = int(m), int(device)
         self._dq_refs = None  # the tensors set_dense_quadratics_device refers to
+        if isinstance(n, np.ndarray) and n.ndim == 0:
+            n = n.item()  # a 0-d array is one size
+        self.ragged = not np.isscalar(n)
         h = C.c_void_p()
-        rc = lib().lbfgs_batch_create(C.byref(h), self.n, self.m, self.batch, int(device))
+        if self.ragged:
+            arr = _sizes_array(n)
+            if batch is not None and int(batch) != len(arr):
+                raise ValueError(f"Batch: {len(arr)} sizes for batch = {batch}")
+            self.batch, self.n = len(arr), int(max(arr))
+            rc = lib().lbfgs_batch_create_ragged(C.byref(h), arr, self.m, self.batch, int(device))
+        else:
+            if batch is None:
+                raise TypeError("Batch: batch is required with one size n")
+            self.n, self.batch = int(n), int(batch)
+            rc = lib().lbfgs_batch_create(C.byref(h), self.n, self.m, self.batch, int(device))
         if rc != 0:
-            e = LbfgsError(f"lbfgs_batch_create failed ({rc})")
+            e = LbfgsError(f"lbfgs_batch_create{'_ragged' if self.ragged else ''} failed ({rc})")
             e.rc = rc
             raise e
         self.h = h
+        sz, of = (C.c_int64 * self.batch)(), (C.c_int64 * (self.batch + 1))()
+        lib().lbfgs_batch_sizes(h, sz, of)
+        self.sizes, self.offsets = [int(v) for v in sz], [int(v) for v in of]
 
     def close(self):
         if getattr(self, "h", None):
@@ -379,6 +430,14 @@ class Batch:
         """Data of objective "dense", problem p minimising x'A[p]x + b[p]'x: A of shape (batch, n, n), or
         (n, n) for one matrix shared by every problem; b of shape (batch, n). float64. Copied to the
         device; may be called again with new data between solves."""
+        if self.ragged:
+            A, b = self._pack(A, "set_dense_quadratics: A", True), self._pack(b, "set_dense_quadratics: b", False)
+            rc = lib().lbfgs_batch_set_dense_quadratics(self.h, A.ctypes.data_as(C.c_void_p), 0,
+                                                        b.ctypes.data_as(C.c_void_p))
+            if rc != 0:
+                self._err("lbfgs_batch_set_dense_quadratics", rc)
+            self._dq_refs = None
+            return
         A, b = np.asarray(A), np.asarray(b)
         if A.dtype != np.float64 or b.dtype != np.float64:
             raise TypeError(f"set_dense_quadratics: A and b must be float64, got {A.dtype} and {b.dtype}")
@@ -393,6 +452,67 @@ class Batch:
         if rc != 0:
             self._err("lbfgs_batch_set_dense_quadratics", rc)
         self._dq_refs = None  # the batch reads its own copies now
+
+    def _pack(self, v, what, square):
+        """A ragged batch's host data as one packed float64 array: a list of `batch` arrays of shapes
+        (n_p,) (square: (n_p, n_p)), or the packed 1-D array itself."""
+        want = [(k, k) if square else (k,) for k in self.sizes]
+        total = sum(k * k if square else k for k in self.sizes)
+        if isinstance(v, np.ndarray) and v.ndim == 1 and v.dtype != object:
+            if v.dtype != np.float64:
+                raise TypeError(f"{what}: float64 is required, got {v.dtype}")
+            if v.shape != (total,):
+                raise ValueError(f"{what}: packed length {v.shape[0]}, expected {total}")
+            return np.ascontiguousarray(v)
+        parts = [np.asarray(q) for q in v]
+        if len(parts) != self.batch:
+            raise ValueError(f"{what}: {len(parts)} arrays for a batch of {self.batch}")
+        for p, q in enumerate(parts):
+            if q.dtype != np.float64:
+                raise TypeError(f"{what}: float64 is required, problem {p} has {q.dtype}")
+            if q.shape != want[p]:
+                raise ValueError(f"{what}: problem {p} has shape {q.shape}, expected {want[p]}")
+        return np.concatenate([q.ravel() for q in parts])
+
+    def _ragged_tensor(self, t, what, square):
+        """Checks a ragged batch's float64 CUDA tensor: padded, (batch, W) or square (batch, W, W) with
+        W >= n, last stride 1 and the other strides >= n (matrices apart); or packed, 1-D contiguous of
+        the sum of n_p (n_p * n_p) elements. Returns (batch stride, row stride), both BATCH_PACKED for a
+        packed tensor; for rows only the batch stride counts. Never a copy."""
+        torch = _torch()
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: a torch tensor is required, got {type(t).__name__}")
+        if t.dtype != torch.float64:
+            raise TypeError(f"{what}: dtype float64 is required, got {t.dtype}")
+        if not t.is_cuda or (t.device.index or 0) != self.device:
+            raise ValueError(f"{what}: a CUDA tensor on device {self.device} is required, got {t.device}")
+        n, B = self.n, self.batch
+        total = sum(k * k if square else k for k in self.sizes)
+        if t.dim() == 1:
+            if t.shape[0] != total or (total > 1 and t.stride(0) != 1):
+                raise ValueError(f"{what}: a packed tensor has {total} elements at stride 1, got shape "
+                                 f"{tuple(t.shape)}, strides {t.stride()}")
+            return BATCH_PACKED, BATCH_PACKED
+        dims = 3 if square else 2
+        if t.dim() != dims or t.shape[0] != B or any(w < n for w in t.shape[1:]) or (square and t.shape[1] != t.shape[2]):
+            raise ValueError(f"{what}: shape {tuple(t.shape)}, expected ({B}, W" + (", W" if square else "") +
+                             f") with W >= {n}, or 1-D packed of {total} elements")
+        st = t.stride()
+        if st[-1] != 1 and t.shape[-1] > 1:
+            raise ValueError(f"{what}: the last dimension must have stride 1, got strides {st} (no copy is made)")
+        if square:
+            lda = st[1] if t.shape[1] > 1 else max(n, 1)
+            if lda < n:
+                raise ValueError(f"{what}: row stride {lda} must be >= the largest n = {n}")
+            bs = st[0] if B > 1 else (n - 1) * lda + n
+            if bs < (n - 1) * lda + n:
+                raise ValueError(f"{what}: batch stride {bs} must be >= (n - 1) * {lda} + n (matrices that do not "
+                                 "interleave); a ragged batch has no shared matrix")
+            return bs, lda
+        ld = st[0] if B > 1 else n
+        if ld < n:
+            raise ValueError(f"{what}: row stride {ld} must be >= the largest n = {n}; a ragged batch has no shared row")
+        return ld, ld
 
     def _rows(self, t, what, shapes, shared_ok):
         """Checks a float64 CUDA tensor on the batch's device whose last stride is 1 and whose other
@@ -426,6 +546,16 @@ class Batch:
         object keeps references to both until they are replaced or close() is called."""
         torch = _torch()
         n, B = self.n, self.batch
+        if self.ragged:
+            abs_, lda = self._ragged_tensor(A, "set_dense_quadratics_device: A", True)
+            ldb, _ = self._ragged_tensor(b, "set_dense_quadratics_device: b", False)
+            torch.cuda.current_stream(self.device).synchronize()
+            rc = lib().lbfgs_batch_set_dense_quadratics_device(self.h, A.data_ptr(), int(abs_), int(lda), b.data_ptr(),
+                                                               int(ldb))
+            if rc != 0:
+                self._err("lbfgs_batch_set_dense_quadratics_device", rc)
+            self._dq_refs = (A, b)
+            return
         sa = self._rows(A, "set_dense_quadratics_device: A", ((B, n, n), (n, n)), getattr(A, "ndim", 0) == 3)
         sb = self._rows(b, "set_dense_quadratics_device: b", ((B, n),), True)
         lda = sa[-2] if n > 1 else n
@@ -449,12 +579,17 @@ class Batch:
         offset is fine. No copy is made. Returns minimize()'s dictionary, bit for bit, with x the tensor."""
         torch = _torch()
         n, B = self.n, self.batch
-        s0 = self._rows(X0, "minimize_device: X0", ((B, n),), True)
-        if out is not None:
-            self._rows(out, "minimize_device: out", ((B, n),), False)
-        X = out if out is not None else torch.empty((B, n), dtype=torch.float64, device=X0.device)
-        ldx0 = s0[0] if B > 1 else n
-        ldx = X.stride(0) if B > 1 else n
+        if self.ragged:  # padded rows (B, W) or one packed tensor; out=None gives X0's form
+            ldx0, _ = self._ragged_tensor(X0, "minimize_device: X0", False)
+            X = out if out is not None else torch.empty_like(X0, memory_format=torch.contiguous_format)
+            ldx, _ = self._ragged_tensor(X, "minimize_device: out", False)
+        else:
+            s0 = self._rows(X0, "minimize_device: X0", ((B, n),), True)
+            if out is not None:
+                self._rows(out, "minimize_device: out", ((B, n),), False)
+            X = out if out is not None else torch.empty((B, n), dtype=torch.float64, device=X0.device)
+            ldx0 = s0[0] if B > 1 else n
+            ldx = X.stride(0) if B > 1 else n
         torch.cuda.current_stream(self.device).synchronize()  # the caller's work on X0 (and A, b) is complete
         res = (Result * B)()
         k = consts if consts is not None else constants()
@@ -473,10 +608,19 @@ class Batch:
         (names; status_code: the numbers), commits, trials_f, trials_fg, h_min, h_max, bytes, and the
         call's launches and seconds; with trace also the lists tr_f / tr_gnorm / tr_alpha and events.
         flags: further LBFGS_FLAG_* bits, passed through (the library refuses what a batch cannot do)."""
-        X0 = np.ascontiguousarray(X0, dtype=np.float64)
-        assert X0.shape == (self.batch, self.n)
-        if out is not None:
-            assert out.dtype == np.float64 and out.shape == X0.shape and out.flags["C_CONTIGUOUS"]
+        if self.ragged:  # a list of per-problem arrays or one packed array; x comes back as a list of views
+            X0 = self._pack(X0, "minimize: X0", False)
+            if out is not None:
+                if not isinstance(out, np.ndarray) or out.dtype != np.float64:
+                    raise TypeError("minimize: out must be a float64 numpy array")
+                if out.shape != X0.shape or not out.flags["C_CONTIGUOUS"]:
+                    raise ValueError(f"minimize: out must be a packed contiguous array of {X0.shape[0]} elements, got shape "
+                                     f"{out.shape}")
+        else:
+            X0 = np.ascontiguousarray(X0, dtype=np.float64)
+            assert X0.shape == (self.batch, self.n)
+            if out is not None:
+                assert out.dtype == np.float64 and out.shape == X0.shape and out.flags["C_CONTIGUOUS"]
         X = out if out is not None else np.zeros_like(X0)
         res = (Result * self.batch)()
         k = consts if consts is not None else constants()
@@ -486,6 +630,8 @@ class Batch:
                                         int(max_iterations), float(tolerance), fl, res)
         if rc < 0:
             self._err("lbfgs_batch_minimize", rc)
+        if self.ragged:
+            X = [X[self.offsets[p]:self.offsets[p + 1]] for p in range(self.batch)]
         return self._results(res, X, trace)
 
     def _results(self, res, X, trace):

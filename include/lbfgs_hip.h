@@ -470,6 +470,32 @@ int lbfgs_batch_minimize_device(lbfgs_batch* b, int objective, int line_search, 
 int lbfgs_batch_set_dense_quadratics_device(lbfgs_batch* b, const double* A_dev, int64_t a_batch_stride,
                                             int64_t lda, const double* b_dev, int64_t ldb);
 
+/* Ragged batches: problems of different sizes in one batch. Problem p has its own
+ * n_p; m, objective, line search, constants, tolerance and iteration limit are shared as before, it
+ * is still one workgroup per problem, and every problem's result (x, f, |g|, iterations, status,
+ * trials, commits, events, trace) is bit for bit lbfgs_minimize's for it alone at n_p. The sizes are
+ * fixed for the life of the object. Limits per problem: 1 <= n_p <= 32768, and <= 4096 for every
+ * problem before a dense setter accepts the batch.
+ *
+ * Everything that was "batch x n doubles, problem p at p*n" is PACKED on a ragged batch: problem p's
+ * n_p doubles at the sum of n_q over q < p (x0_host, x_out_host and b of the host forms), its n_p x n_p
+ * row-major matrix at the sum of n_q*n_q (A of lbfgs_batch_set_dense_quadratics; shared_A = 1 is
+ * refused). In the device forms every stride of rows (ldx0, ldx, ldb; the pair a_batch_stride and lda
+ * together) is either a stride as before, measured against the largest n_p, with only [0, n_p) of
+ * problem p's row read or written, or LBFGS_BATCH_PACKED for the packed layout (A's rows then n_p
+ * apart). The strides 0 (one x0, one A, one b for all) are refused on a ragged batch, and
+ * LBFGS_BATCH_PACKED is refused on a uniform one. lbfgs_result.bytes of problem p counts n_p. */
+#define LBFGS_BATCH_PACKED (-1)
+/* no device needed: 0 when every n[p] (and m, batch) is within the limits above (those of a dense
+ * batch when `dense`), else LBFGS_ERR_BAD_ARG; *bytes (nullable) = device memory the batch would take:
+ * per problem what lbfgs_batch_plan(n_p, m, 1) gives plus 52 bytes of the table (a row of six 64-bit
+ * values and a 4-byte entry of the order of work), and with `dense` also t, gt, b and the matrix */
+int lbfgs_batch_ragged_plan(const int64_t* n, int batch, int m, int dense, double* bytes);
+int lbfgs_batch_create_ragged(lbfgs_batch** out, const int64_t* n, int m, int batch, int device);
+/* n_out: batch sizes; offset_out: batch + 1 packed offsets (the last is the sum of the sizes); either
+ * may be NULL. A uniform batch reports n and p*n. */
+int lbfgs_batch_sizes(const lbfgs_batch* b, int64_t* n_out, int64_t* offset_out);
+
 /* ---- canonical reductions on caller-owned device buffers -------------------------------- */
 /* For objectives evaluated on the device (LBFGS_OBJ_DEVICE): the sum of their per-element terms in
  * the solver's canonical fixed order, so that f is reproducible run to run and
