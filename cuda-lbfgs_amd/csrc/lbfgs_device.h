@@ -142,6 +142,10 @@ int lbk_coop_info(const lbk_ctx* c, int* coop_max, int* search_max, int* fallbac
 int lbk_wait_stats(const lbk_ctx* c, double* slept_s, unsigned long long* waits, int* adaptive);
 /* vectors allocated with a plain hipMalloc because a physically contiguous one was refused */
 int lbk_vec_fallbacks(const lbk_ctx* c);
+/* split work vector (LBFGS_WORK_SPLIT), process-wide counters since the library was loaded: split
+ * passes, consolidation copies of a displaced middle, failed allocations of the alternate buffer,
+ * displaced middles given up. The device layer's own export: the driver does not call it. */
+void lbk_work_split_stats(unsigned long long* out4);
 /* the context's allocation mode (0 pool, 1 plain, 2 contiguous), its vectors taken from or added
  * to the process-wide contiguous pool, and the GiB the pool owns */
 int lbk_vec_pool_stats(const lbk_ctx* c, int* pooled, double* held_gb);

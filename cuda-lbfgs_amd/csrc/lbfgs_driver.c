@@ -1606,8 +1606,12 @@ static int iterate(lbfgs_ctx* c) {
                     DEV(lbk_dot(c->dev, c->S[top], c->g, SLOT_P0));
                     refA[h - 1] = REF(SLOT_P0, 0);
                 }
-                /* q and r are updated in place (the passes' q/r stay in the Infinity Cache; a
-                 * ping-pong between two buffers measured neutral at 1e8 and -8 % at 1e7) */
+                /* q and r are updated in place as far as the driver is concerned. The device layer
+                 * keeps the two ends of each vector in place - the tail the alternating walk re-reads
+                 * from the Infinity Cache - and ping-pongs the segments between them through an
+                 * alternate buffer of its own (LBFGS_WORK_SPLIT, DESIGN.md §4 "Split work vector").
+                 * A ping-pong of the whole vectors measured neutral at 1e8 and -8 % at 1e7: it gives
+                 * up the cached ends. */
                 const double* qsrc = c->g;
                 for (int i = h - 2; i >= 0; --i) {
                     DEV(lbk_axpy_dot(c->dev, c->q, qsrc, c->Y[c->ring[i + 1]], c->S[c->ring[i]], rho[i + 1],

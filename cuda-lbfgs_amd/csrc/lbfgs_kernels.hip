@@ -393,6 +393,51 @@ int lbk_create(lbk_ctx** out, int device, int64_t n, int rank, int world, const 
         else if (atoi(e) != 0)
             c->ug_on = 0;
     }
+    // LBFGS_WORK_SPLIT ("Split work vector"): 0 - off; W - on, the end windows are W
+    // segments each (Wlo:Whi - the low and the high end's; 0:0 - no windows), at any n; <n>MB - on,
+    // windows of n 10^6 bytes of the work vector each, which carries over to other n; "poison" (alone:
+    // the default window; or after a comma: "3,poison") - the stale copy of the middle is filled with
+    // NaN after every split pass (tests: a reader that was missed shows up in a bit-compare). Unset:
+    // the default window (kWsWindowBytes). In scope: one rank, the launch sequence; without a window
+    // given in segments only vectors above the non-temporal threshold. Where the two windows cover
+    // every segment (n up to 5e7 by default) there is no middle and the path is the unsplit one.
+    // LBFGS_WORK_SPLIT_NT: 1 (default) - the middle streams non-temporal, only the windows occupy
+    // the cache; 0 - the work vectors' temporal policy.
+    c->ws = lbk_ctx::Ws{};
+    const char* ws_env = getenv("LBFGS_WORK_SPLIT");
+    const bool ws_default = !ws_env && kWsDefaultOn;
+    if (ws_default) ws_env = "default";  // (no number, no poison: the default window)
+    if (const char* e = ws_env) {
+        const bool scope = world == 1 && !grp && !nccl_id && !(c->coop_max > 0 && G.nseg <= c->coop_max) &&
+                           persist_grid(c) == 0;
+        // "<spec>[,poison]" | "poison"; spec: "0" | W | Wlo:Whi | <n>MB
+        const char* comma = strchr(e, ',');
+        c->ws.poison = !strcmp(comma ? comma + 1 : e, "poison");
+        int64_t wlo = -1, whi = -1;  // segments per end (-1: off)
+        bool forced = false;         // an explicit window in segments: any n
+        char* end = nullptr;
+        const long long v = strtoll(e, &end, 10);
+        if (end == e) {  // no number ("poison" alone, or the default): the default window
+            if (c->ws.poison || ws_default) wlo = whi = (kWsWindowBytes / 8 + G.L - 1) / G.L;
+        } else if (!strncmp(end, "MB", 2)) {
+            wlo = whi = ((int64_t)v * 1000000 / 8 + G.L - 1) / G.L;
+        } else if (*end == ':') {
+            wlo = v;
+            whi = strtoll(end + 1, nullptr, 10);
+            forced = true;
+        } else if (v > 0) {
+            wlo = whi = v;
+            forced = true;
+        }
+        if (wlo >= 0 && whi >= 0 && scope && (forced || c->nt)) {
+            const int64_t nb = G.seg_hi - G.seg_lo;
+            c->ws.lo = (int)std::min<int64_t>(wlo, nb);
+            c->ws.hi = (int)std::max<int64_t>(nb - whi, c->ws.lo);
+            c->ws.on = c->ws.hi > c->ws.lo;
+        }
+        c->ws.nt = 1;  // (measured: the middle non-temporal is the better policy at every window)
+        if (const char* t = getenv("LBFGS_WORK_SPLIT_NT")) c->ws.nt = atoi(t) != 0;
+    }
     if (!grp && nccl_id) return rccl_init(c, nccl_id);
     return 0;
 }
@@ -504,6 +549,7 @@ void lbk_destroy(lbk_ctx* c) {
     if (c->dq_A) (void)hipFree(c->dq_A);
     if (c->dq_b) (void)hipFree(c->dq_b);
     if (c->dq_t) (void)hipFree(c->dq_t - LBK_FRONT);
+    if (c->ws.alt) lbk_vec_free(c, c->ws.alt);
     lbk_xgmi_destroy(c->xg);
     if (c->d_ckslot) (void)hipFree(c->d_ckslot);
     (void)hipFree(c->partials);
@@ -865,6 +911,18 @@ int lbk_dot(lbk_ctx* c, const double* a, const double* b, int slot) {
     });
 }
 
+// a pass kernel's split-work-vector variant: 1 - the middle in its own buffer, 2 - and non-temporal
+#define WS_DISPATCH(c, ...)                            \
+    do {                                               \
+        if ((c)->ws.nt) {                              \
+            constexpr int WS_ = 2;                     \
+            __VA_ARGS__;                               \
+        } else {                                       \
+            constexpr int WS_ = 1;                     \
+            __VA_ARGS__;                               \
+        }                                              \
+    } while (0)
+
 int lbk_axpy_dot(lbk_ctx* c, double* qout, const double* qin, const double* y, const double* s, double rho,
                  int ref_alpha, int slot) {
     // q_in an unstored gradient: the pass forms it from its x (entries exist on one rank only)
@@ -872,11 +930,18 @@ int lbk_axpy_dot(lbk_ctx* c, double* qout, const double* qin, const double* y, c
     const bool from_x = ui >= 0 && !c->ug[ui].stored && c->ug[ui].x != qout;
     const double* ux = from_x ? c->ug[ui].x : nullptr;
     const int uobj = from_x ? c->ug[ui].obj : 0;
+    // in place: the pass of a split work vector (ws_pass); any other source is read whole and
+    // q_out is written whole
+    const bool inplace = qout == qin;
     if (!from_x)
-        if (const int rc_ = ug_in(c, qin)) return rc_;
+        if (const int rc_ = ug_in(c, qin, !inplace)) return rc_;
     if (const int rc_ = ug_in(c, y)) return rc_;
     if (const int rc_ = ug_in(c, s)) return rc_;
-    if (const int rc_ = ug_out(c, {qout})) return rc_;
+    WSplit ws{nullptr, nullptr, 0, 0};
+    if (inplace) {
+        if (const int rc_ = ws_pass(c, qout, ws)) return rc_;
+    }
+    if (const int rc_ = ug_out(c, {qout}, !inplace)) return rc_;
     Geo g = kgeo(c);
     g.ppart = take_pending(c, ref_alpha);
     const FoldSrc fs = take_fold(c, ref_alpha);
@@ -888,18 +953,24 @@ int lbk_axpy_dot(lbk_ctx* c, double* qout, const double* qin, const double* y, c
             OBJ_DISPATCH(uobj, hipLaunchKernelGGL((k_axpy_dot_x<O_, NT_>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, qout, ux, y, s, rho, pa, g, r));
             return 0;
         });
-    return launch(c, LBK_K_AXPY_DOT, 4, slot, [&] {
-        if (r.fp.peers || fs.mbx)
-            NT_DISPATCH(c, hipLaunchKernelGGL((k_axpy_dot<NT_, true>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, qout, qin, y, s, rho, pa, g, r, fs));
+    const int rc = launch(c, LBK_K_AXPY_DOT, 4, slot, [&] {
+        if (ws.mout)
+            NT_DISPATCH(c, WS_DISPATCH(c, hipLaunchKernelGGL((k_axpy_dot<NT_, false, WS_>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, qout, qin, y, s, rho, pa, g, r, fs, ws)));
+        else if (r.fp.peers || fs.mbx)
+            NT_DISPATCH(c, hipLaunchKernelGGL((k_axpy_dot<NT_, true>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, qout, qin, y, s, rho, pa, g, r, fs, ws));
         else
-            NT_DISPATCH(c, hipLaunchKernelGGL(k_axpy_dot<NT_>, dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, qout, qin, y, s, rho, pa, g, r, fs));
+            NT_DISPATCH(c, hipLaunchKernelGGL(k_axpy_dot<NT_>, dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, qout, qin, y, s, rho, pa, g, r, fs, ws));
     });
+    return rc ? rc : ws_poison(c, ws);
 }
 
 int lbk_mid(lbk_ctx* c, double* rout, const double* qin, const double* y0, double rho0, double gamma,
             int ref_alpha, int slot) {
-    if (const int rc_ = ug_in(c, qin)) return rc_;
+    // q may be a split work vector: read through the select; r is written whole
+    if (const int rc_ = ug_in(c, qin, rout == qin)) return rc_;
     if (const int rc_ = ug_in(c, y0)) return rc_;
+    WSplit ws;
+    if (const int rc_ = ws_reader(c, qin, ws)) return rc_;
     if (const int rc_ = ug_out(c, {rout})) return rc_;
     Geo g = kgeo(c);
     g.ppart = take_pending(c, ref_alpha);
@@ -909,19 +980,26 @@ int lbk_mid(lbk_ctx* c, double* rout, const double* qin, const double* y0, doubl
     const double* pa = sref(c, ref_alpha);
     if (c->geo.world > 1) g.edge_slot = r.slot;
     return launch(c, LBK_K_MID, 3, slot, [&] {
-        if (r.fp.peers || fs.mbx)
-            NT_DISPATCH(c, hipLaunchKernelGGL((k_mid<NT_, true>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, rout, qin, y0, rho0, gamma, pa, g, r, fs));
+        if (ws.min)
+            NT_DISPATCH(c, hipLaunchKernelGGL((k_mid<NT_, false, 1>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, rout, qin, y0, rho0, gamma, pa, g, r, fs, ws));
+        else if (r.fp.peers || fs.mbx)
+            NT_DISPATCH(c, hipLaunchKernelGGL((k_mid<NT_, true>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, rout, qin, y0, rho0, gamma, pa, g, r, fs, ws));
         else
-            NT_DISPATCH(c, hipLaunchKernelGGL(k_mid<NT_>, dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, rout, qin, y0, rho0, gamma, pa, g, r, fs));
+            NT_DISPATCH(c, hipLaunchKernelGGL(k_mid<NT_>, dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, rout, qin, y0, rho0, gamma, pa, g, r, fs, ws));
     });
 }
 
 int lbk_axpy2_dot(lbk_ctx* c, double* rr, const double* rin, const double* s, const double* ynext, double rho,
                   int ref_beta, int ref_alpha, int slot) {
-    if (const int rc_ = ug_in(c, rin)) return rc_;
+    const bool inplace = rr == rin;  // (as lbk_axpy_dot)
+    if (const int rc_ = ug_in(c, rin, !inplace)) return rc_;
     if (const int rc_ = ug_in(c, s)) return rc_;
     if (const int rc_ = ug_in(c, ynext)) return rc_;
-    if (const int rc_ = ug_out(c, {rr})) return rc_;
+    WSplit ws{nullptr, nullptr, 0, 0};
+    if (inplace) {
+        if (const int rc_ = ws_pass(c, rr, ws)) return rc_;
+    }
+    if (const int rc_ = ug_out(c, {rr}, !inplace)) return rc_;
     Geo g = kgeo(c);
     g.ppart = take_pending(c, ref_beta);
     const FoldSrc fs = take_fold(c, ref_beta);
@@ -930,19 +1008,24 @@ int lbk_axpy2_dot(lbk_ctx* c, double* rr, const double* rin, const double* s, co
     const double* pb = sref(c, ref_beta);
     const double* pa = sref(c, ref_alpha);
     if (c->geo.world > 1) g.edge_slot = r.slot;
-    return launch(c, LBK_K_AXPY2_DOT, 4, slot, [&] {
-        if (r.fp.peers || fs.mbx)
-            NT_DISPATCH(c, hipLaunchKernelGGL((k_axpy2_dot<NT_, true>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, rr, rin, s, ynext, rho, pb, pa, g, r, fs));
+    const int rc = launch(c, LBK_K_AXPY2_DOT, 4, slot, [&] {
+        if (ws.mout)
+            NT_DISPATCH(c, WS_DISPATCH(c, hipLaunchKernelGGL((k_axpy2_dot<NT_, false, WS_>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, rr, rin, s, ynext, rho, pb, pa, g, r, fs, ws)));
+        else if (r.fp.peers || fs.mbx)
+            NT_DISPATCH(c, hipLaunchKernelGGL((k_axpy2_dot<NT_, true>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, rr, rin, s, ynext, rho, pb, pa, g, r, fs, ws));
         else
-            NT_DISPATCH(c, hipLaunchKernelGGL(k_axpy2_dot<NT_>, dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, rr, rin, s, ynext, rho, pb, pa, g, r, fs));
+            NT_DISPATCH(c, hipLaunchKernelGGL(k_axpy2_dot<NT_>, dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, rr, rin, s, ynext, rho, pb, pa, g, r, fs, ws));
     });
+    return rc ? rc : ws_poison(c, ws);
 }
 
 int lbk_last(lbk_ctx* c, double* dout, const double* rr, const double* s, const double* gg, double rho,
              int ref_beta, int ref_alpha, int slot) {
-    if (const int rc_ = ug_in(c, rr)) return rc_;
+    if (const int rc_ = ug_in(c, rr, dout == rr)) return rc_;  // (a split r: read through the select)
     if (const int rc_ = ug_in(c, s)) return rc_;
     if (const int rc_ = ug_in(c, gg)) return rc_;
+    WSplit ws;
+    if (const int rc_ = ws_reader(c, rr, ws)) return rc_;
     if (const int rc_ = ug_out(c, {dout})) return rc_;
     Geo g = kgeo(c);
     g.ppart = take_pending(c, ref_beta);
@@ -951,7 +1034,10 @@ int lbk_last(lbk_ctx* c, double* dout, const double* rr, const double* s, const 
     const double* pa = sref(c, ref_alpha);
     if (c->geo.world > 1) g.edge_slot = r.slot;
     return launch(c, LBK_K_LAST, 4, slot, [&] {
-        NT_DISPATCH(c, hipLaunchKernelGGL(k_last<NT_>, dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, dout, rr, s, gg, rho, pb, pa, g, r));
+        if (ws.min)
+            NT_DISPATCH(c, hipLaunchKernelGGL((k_last<NT_, 1>), dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, dout, rr, s, gg, rho, pb, pa, g, r, ws));
+        else
+            NT_DISPATCH(c, hipLaunchKernelGGL(k_last<NT_>, dim3(nblocks(c)), dim3(LB_BLOCK), 0, c->stream, dout, rr, s, gg, rho, pb, pa, g, r, ws));
     });
 }
 
@@ -1693,6 +1779,14 @@ int lbk_cu_partition(const lbk_ctx* c) { return c->cu_part ? c->cu_count : 0; }
 
 int lbk_vec_fallbacks(const lbk_ctx* c) { return c->vec_plain_fallbacks; }
 
+unsigned long long* lbk_ws_counters(void) {
+    static unsigned long long counters[4];
+    return counters;
+}
+void lbk_work_split_stats(unsigned long long* out4) {
+    for (int i = 0; i < 4; ++i) out4[i] = lbk_ws_counters()[i];
+}
+
 int lbk_wait_stats(const lbk_ctx* c, double* slept_s, unsigned long long* waits, int* adaptive) {
     if (slept_s) *slept_s = c->wait_slept_s;
     if (waits) *waits = c->waits;
@@ -1709,6 +1803,7 @@ int lbk_coop_info(const lbk_ctx* c, int* coop_max, int* search_max, int* fallbac
 
 int lbk_stream_probe(lbk_ctx* c, double* q, const double* const* ys, const double* const* ss, int npairs,
                      int launches, double* us, int variant, double* const* outs) {
+    if (const int rc_ = ws_whole_all(c)) return rc_;  // (the probe reads q as well)
     if (const int rc_ = ug_out(c, {q})) return rc_;
     if (launches < 1 || !us || !q || !ys || !ss || npairs < 1) return -1;
     for (int k = 0; k < npairs; ++k)

@@ -20,7 +20,8 @@ int lbk_commit(lbk_ctx* c, int obj, int dmode, const double* x, const double* ds
     if (!ug)
         if (const int rc_ = ug_in(c, gg)) return rc_;
     if (const int rc_ = ug_in(c, x)) return rc_;
-    if (const int rc_ = ug_in(c, dsrc)) return rc_;
+    // (a split r is read through DirArgs' select, ws_dir; D_NEG_G does not read dsrc)
+    if (const int rc_ = ug_in(c, dsrc, dmode == LBK_D_BUF)) return rc_;
     if (const int rc_ = ug_in(c, s_last)) return rc_;
     if (obj == LBK_OBJ_NONE) {  // g_new is an input
         if (const int rc_ = ug_in(c, gn)) return rc_;
@@ -34,6 +35,7 @@ int lbk_commit(lbk_ctx* c, int obj, int dmode, const double* x, const double* ds
         Red r = kred(c, slot, with_cand ? 8 : 7);
         DirArgs da = {dsrc, s_last, nullptr, 0.0, sref(c, ref_alpha), sref(c, ref_beta), rho, nullptr, c->geo.g_lo,
                       c->geo.g_hi};
+        if (const int rc_ = ws_dir(c, da)) return rc_;
         g.ppart = take_pending(c, ref_beta);
         // 3 R (x, r, s_last) + 3 W (x_new, s, y)
         const int rc = launch(c, LBK_K_COMMIT, 6.0, slot, [&] {
@@ -73,6 +75,7 @@ static int lbk_commit_stored(lbk_ctx* c, int obj, int dmode, const double* x, co
     if (dmode == LBK_D_TWOLOOP) {
         da.pa = sref(c, ref_alpha);
         da.pb = sref(c, ref_beta);
+        if (const int rc_ = ws_dir(c, da)) return rc_;
         g.ppart = take_pending(c, ref_beta);
     }
     double passes = 4.0 + (dmode == LBK_D_BUF ? 3.0 : dmode == LBK_D_NEG_G ? 2.0 : 4.0);
@@ -116,7 +119,7 @@ int lbk_trials(lbk_ctx* c, int obj, int dmode, const double* x, const double* ds
                const double* gg, double rho, int ref_beta, int ref_alpha, const double* alphas, int nc, int dphi,
                int slot) {
     if (const int rc_ = ug_in(c, x)) return rc_;
-    if (const int rc_ = ug_in(c, dsrc)) return rc_;
+    if (const int rc_ = ug_in(c, dsrc, dmode == LBK_D_BUF)) return rc_;  // (as lbk_commit)
     if (const int rc_ = ug_in(c, s_last)) return rc_;
     if (dmode == LBK_D_NEG_G)  // the only direction mode that reads g
         if (const int rc_ = ug_in(c, gg)) return rc_;
@@ -132,6 +135,7 @@ int lbk_trials(lbk_ctx* c, int obj, int dmode, const double* x, const double* ds
     if (dmode == LBK_D_TWOLOOP) {
         da.pa = sref(c, ref_alpha);
         da.pb = sref(c, ref_beta);
+        if (const int rc_ = ws_dir(c, da)) return rc_;
         g.ppart = take_pending(c, ref_beta);
     }
     const double passes = dmode == LBK_D_TWOLOOP ? 3.0 : 2.0;

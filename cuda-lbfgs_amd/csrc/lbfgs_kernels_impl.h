@@ -79,6 +79,16 @@ struct FoldSrc {
     unsigned long long* wait;  // profiling: workgroup 0 adds its prologue's wall-clock ticks here
 };
 
+// Split work vector (one rank, the launch sequence; DESIGN.md §4, "Split work vector"): the segments
+// [lo, hi) of this launch, counted from the rank's first, read their q / r from `min` and write it
+// to `mout` - the two buffers of a ping-pong pair - while the segments outside (the end windows the
+// alternating walk keeps in the Infinity Cache) stay in place in the pass's own buffer. A separate
+// kernel argument, as FoldSrc: Geo stays as it is. lo >= hi: no middle.
+struct WSplit {
+    const double* min;
+    double* mout;
+    int lo, hi;
+};
 // Folded exchange, producer side: where a pass pushes its group values (stage 2's last arriver,
 // or k_group_reduce) and its rank-edge values (publish_edges) - every peer's mailbox at `epoch`,
 // in the exchange kernel's wire format (lbfgs_xgmi.h). peers == nullptr: no push.
@@ -237,6 +247,12 @@ struct Seg {
 // this workgroup's segment, relative to the rank's first: launch order or reversed
 __device__ __forceinline__ int64_t seg_block(const Geo& geo) {
     return geo.rev ? (int64_t)gridDim.x - 1 - blockIdx.x : (int64_t)blockIdx.x;
+}
+
+// split work vector: this workgroup's segment lies in the middle (uniform over the workgroup)
+__device__ __forceinline__ bool ws_mid(const WSplit& ws, const Geo& geo) {
+    const int64_t b = seg_block(geo);
+    return b >= ws.lo && b < ws.hi;
 }
 
 __device__ __forceinline__ Seg seg_setup(const Geo& geo) {
@@ -912,7 +928,9 @@ struct OpDot {  // acc += a . b
     }
 };
 
-template <bool NT>
+// WNT: the work vector streams non-temporal too (the middle of a split work vector under
+// LBFGS_WORK_SPLIT_NT=1: only the end windows are meant to occupy the cache)
+template <bool NT, bool WNT = false>
 struct OpAxpyDot {  // q = qin - alpha y;  acc += s . q       (lbfgs.cpp:133-137)
     double* qout;
     const double* qin;
@@ -924,7 +942,7 @@ struct OpAxpyDot {  // q = qin - alpha y;  acc += s . q       (lbfgs.cpp:133-137
         double2 q, y, s;
     };
     __device__ void load(Row& r, int64_t i) const {
-        r.q = ldw(qin + i);
+        r.q = ldv<WNT>(qin + i);
         r.y = ldv<NT>(y + i);
         r.s = ldv<NT>(s + i);
     }
@@ -933,7 +951,7 @@ struct OpAxpyDot {  // q = qin - alpha y;  acc += s . q       (lbfgs.cpp:133-137
         double2 qn;
         qn.x = r.q.x - alpha * r.y.x;
         qn.y = r.q.y - alpha * r.y.y;
-        st2w<MASK>(qout + i, qn, v0, v1);
+        st2<MASK, WNT>(qout + i, qn, v0, v1);
         acc[0] = fma2<MASK>(r.s, qn, acc[0], v0, v1);
     }
 };
@@ -978,7 +996,7 @@ struct OpMid {  // r = (qin - alpha0 y0) * gamma;  acc += y0 . r      (:134-137,
     }
 };
 
-template <bool NT>
+template <bool NT, bool WNT = false>
 struct OpAxpy2Dot {  // r += s (alpha - beta);  acc += ynext . r      (:159-164)
     double* r;        // out (== rin in place, or the other buffer of a ping-pong pair)
     const double* rin;
@@ -993,7 +1011,7 @@ struct OpAxpy2Dot {  // r += s (alpha - beta);  acc += ynext . r      (:159-164)
         double2 r, s, y;
     };
     __device__ void load(Row& w, int64_t i) const {
-        w.r = ldw(rin + i);
+        w.r = ldv<WNT>(rin + i);
         w.s = ldv<NT>(s + i);
         w.y = ldv<NT>(yn + i);
     }
@@ -1002,7 +1020,7 @@ struct OpAxpy2Dot {  // r += s (alpha - beta);  acc += ynext . r      (:159-164)
         double2 rn;
         rn.x = w.r.x + w.s.x * coef;
         rn.y = w.r.y + w.s.y * coef;
-        st2w<MASK>(r + i, rn, v0, v1);
+        st2<MASK, WNT>(r + i, rn, v0, v1);
         publish_edges(edge_slot, i, n_loc, g_lo, g_hi, rn, v0, v1);
         acc[0] = fma2<MASK>(w.y, rn, acc[0], v0, v1);
     }
@@ -1135,10 +1153,30 @@ __global__ __launch_bounds__(LB_BLOCK) void k_dot(const double* __restrict__ a, 
 // FOLD: sharded over the mailboxes, the source arrives folded (src_total polls) and the result is
 // pushed folded. A folded producer whose source came through a slot (or the reverse) does not
 // occur: the two-loop's passes fold as a chain.
-template <bool NT, bool FOLD = false>
+// WS (split work vector, never with FOLD): 1 - a middle workgroup reads ws.min and writes ws.mout,
+// one workgroup-uniform select ahead of the stream, which is run_pass either way: the same rows,
+// unroll, accumulation order and partials, so the same bits; 2 - the middle also streams q
+// non-temporal (its own copy of the loop, chosen per workgroup).
+template <bool NT, bool FOLD = false, int WS = 0>
 __global__ __launch_bounds__(LB_BLOCK) void k_axpy_dot(double* qout, const double* qin, const double* __restrict__ y,
                                                        const double* __restrict__ sv, double rho,
-                                                       const double* __restrict__ prev, Geo geo, Red red, FoldSrc fs) {
+                                                       const double* __restrict__ prev, Geo geo, Red red, FoldSrc fs,
+                                                       WSplit ws) {
+    static_assert(!(FOLD && WS), "a split work vector is a one-rank form");
+    if constexpr (WS != 0) {
+        const bool mid = ws_mid(ws, geo);
+        if (mid) {
+            qin = ws.min;
+            qout = ws.mout;
+        }
+        if constexpr (WS == 2) {
+            if (mid) {
+                const double alpha = rho * src_total(prev, geo);
+                run_pass<OpAxpyDot<NT, true>, 1>(OpAxpyDot<NT, true>{qout, qin, y, sv, alpha}, geo, red);
+                return;
+            }
+        }
+    }
     if constexpr (FOLD) {
         if (fs.mbx) {
             run_pass_prefetch<OpAxpyDot<NT>, 1>(OpAxpyDot<NT>{qout, qin, y, sv, 0.0}, geo, red,
@@ -1150,10 +1188,16 @@ __global__ __launch_bounds__(LB_BLOCK) void k_axpy_dot(double* qout, const doubl
     run_pass<OpAxpyDot<NT>, 1, FOLD>(OpAxpyDot<NT>{qout, qin, y, sv, alpha}, geo, red);
 }
 
-template <bool NT, bool FOLD = false>
+// WS = 1: q is a split work vector whose middle lives in ws.min; r is written whole
+template <bool NT, bool FOLD = false, int WS = 0>
 __global__ __launch_bounds__(LB_BLOCK) void k_mid(double* __restrict__ rout, const double* __restrict__ qin,
                                                   const double* __restrict__ y0, double rho0, double gamma,
-                                                  const double* __restrict__ prev, Geo geo, Red red, FoldSrc fs) {
+                                                  const double* __restrict__ prev, Geo geo, Red red, FoldSrc fs,
+                                                  WSplit ws) {
+    static_assert(!(FOLD && WS), "a split work vector is a one-rank form");
+    if constexpr (WS != 0) {
+        if (ws_mid(ws, geo)) qin = ws.min;
+    }
     if constexpr (FOLD) {
         if (fs.mbx) {
             run_pass_prefetch<OpMid<NT>, 1>(OpMid<NT>{rout, qin, y0, 0.0, gamma, geo.edge_slot, geo.n_loc, geo.g_lo,
@@ -1168,11 +1212,30 @@ __global__ __launch_bounds__(LB_BLOCK) void k_mid(double* __restrict__ rout, con
 }
 
 // beta = rho * total(pb), alpha = rho * total(pa)
-template <bool NT, bool FOLD = false>
+// WS: as k_axpy_dot
+template <bool NT, bool FOLD = false, int WS = 0>
 __global__ __launch_bounds__(LB_BLOCK) void k_axpy2_dot(double* r, const double* rin, const double* __restrict__ sv,
                                                         const double* __restrict__ yn, double rho,
                                                         const double* __restrict__ pb, const double* __restrict__ pa,
-                                                        Geo geo, Red red, FoldSrc fs) {
+                                                        Geo geo, Red red, FoldSrc fs, WSplit ws) {
+    static_assert(!(FOLD && WS), "a split work vector is a one-rank form");
+    if constexpr (WS != 0) {
+        const bool mid = ws_mid(ws, geo);
+        if (mid) {
+            rin = ws.min;
+            r = ws.mout;
+        }
+        if constexpr (WS == 2) {
+            if (mid) {
+                const double beta = rho * src_total(pb, geo);
+                const double alpha = rho * slot_total(pa);
+                run_pass<OpAxpy2Dot<NT, true>, 1>(
+                    OpAxpy2Dot<NT, true>{r, rin, sv, yn, alpha - beta, geo.edge_slot, geo.n_loc, geo.g_lo, geo.g_hi}, geo,
+                    red);
+                return;
+            }
+        }
+    }
     if constexpr (FOLD) {
         if (fs.mbx) {
             run_pass_prefetch<OpAxpy2Dot<NT>, 1>(
@@ -1190,11 +1253,15 @@ __global__ __launch_bounds__(LB_BLOCK) void k_axpy2_dot(double* r, const double*
         OpAxpy2Dot<NT>{r, rin, sv, yn, alpha - beta, geo.edge_slot, geo.n_loc, geo.g_lo, geo.g_hi}, geo, red);
 }
 
-template <bool NT>
+// WS = 1: r is a split work vector whose middle lives in ws.min
+template <bool NT, int WS = 0>
 __global__ __launch_bounds__(LB_BLOCK) void k_last(double* __restrict__ dout, const double* __restrict__ r,
                                                    const double* __restrict__ sv, const double* __restrict__ g,
                                                    double rho, const double* __restrict__ pb,
-                                                   const double* __restrict__ pa, Geo geo, Red red) {
+                                                   const double* __restrict__ pa, Geo geo, Red red, WSplit ws) {
+    if constexpr (WS != 0) {
+        if (ws_mid(ws, geo)) r = ws.min;
+    }
     const double beta = rho * src_total(pb, geo);
     const double alpha = rho * slot_total(pa);
     run_pass<OpLast<NT>, 1>(OpLast<NT>{dout, r, sv, g, alpha - beta, geo.edge_slot, geo.n_loc, geo.g_lo, geo.g_hi},
@@ -1227,7 +1294,26 @@ struct DirArgs {
     unsigned redge_seq;
     unsigned* err;
     unsigned long long tmo;
+    // D_TWOLOOP, split work vector: the elements [alo, ahi) of r live in dalt, not in dsrc (nullptr:
+    // r is whole). dir_split (the kernel's prologue) points dsrc at this workgroup's own part and
+    // keeps the pass's buffer in dmain for the halo elements, which may lie across the boundary.
+    const double* dalt;
+    int64_t alo, ahi;
+    const double* dmain;
 };
+
+// split work vector, the readers' prologue: one workgroup-uniform select of the row loads' source
+__device__ __forceinline__ void dir_split(DirArgs& da, const Geo& geo) {
+    if (!da.dalt) return;
+    da.dmain = da.dsrc;
+    const int64_t e = seg_block(geo) * geo.L;  // (one rank: local = global)
+    if (e >= da.alo && e < da.ahi) da.dsrc = da.dalt;
+}
+// r at a single element (halos): the buffer that holds element i
+__device__ __forceinline__ const double* dir_base(const DirArgs& da, int64_t i) {
+    if (!da.dalt) return da.dsrc;
+    return (i >= da.alo && i < da.ahi) ? da.dalt : da.dmain;
+}
 
 // The direction source (d, or r of the last second-loop pass) is a work vector: the commit and the
 // trials read it temporal (streaming it non-temporal was measured and removed).
@@ -1251,7 +1337,7 @@ template <int DMODE>
 __device__ __forceinline__ double load_dir1(const DirArgs& da, int64_t i) {
     if (DMODE == LBK_D_BUF) return da.dsrc[i];
     if (DMODE == LBK_D_NEG_G) return -da.g[i];
-    return -(da.dsrc[i] + da.s[i] * da.coef);
+    return -(dir_base(da, i)[i] + da.s[i] * da.coef);
 }
 
 // neighbour rank's edge d, from the all-gathered slot (see publish_edges)
@@ -1522,6 +1608,7 @@ __global__ __launch_bounds__(LB_BLOCK) void k_commit(const double* __restrict__ 
         const double beta = da.rho * src_total(da.pb, geo);
         const double alph = da.rho * slot_total(da.pa);
         da.coef = alph - beta;  // r[j] += s[j] * (alpha[i] - beta)  (lbfgs.cpp:137)
+        dir_split(da, geo);
     }
     // sharded: keep the x and s ghosts current (x_new = x + alpha d and s = x_new - x at the
     // neighbours' edge elements: the owner's operands, so the owner's bits). The s ghosts let a
@@ -1663,6 +1750,7 @@ __global__ __launch_bounds__(LB_BLOCK) void k_trials(Geo geo, Red red, OpTrials<
         const double beta = op.da.rho * src_total(op.da.pb, geo);
         const double alph = op.da.rho * slot_total(op.da.pa);
         op.da.coef = alph - beta;
+        dir_split(op.da, geo);
     }
     run_pass_halo<OpTrials<OBJ, DMODE, NC, DPHI, NT>, OpTrials<OBJ, DMODE, NC, DPHI, NT>::K>(op, geo, red);
 }
@@ -3121,7 +3209,38 @@ struct lbk_ctx {
     Ug ug[2];
     int ug_on;      // entries are made: one rank, the launch sequence, no persistent two-loop
     int ug_poison;  // LBFGS_STORE_G=poison: an unstored gradient's buffer is filled with NaN (tests)
+    // Split work vector (LBFGS_WORK_SPLIT). An in-place two-loop pass (lbk_axpy_dot /
+    // lbk_axpy2_dot with out == in) updates the end windows - segments outside [lo, hi) - in place and
+    // moves the middle between the pass's buffer `main` and the context's alternate buffer `alt`
+    // (out of place: plain HBM streams that faster); `displaced`: the middle of `main` lives in alt.
+    // The passes that follow read through the same select (k_mid, k_last, the TWOLOOP commit and
+    // trials); a fresh writer writes the whole vector to its buffer; every other entry point has a
+    // displaced middle copied back first (ws_whole, from ug_in / ug_out / ug_flush). The pair shares
+    // one alt: when the other work vector starts its in-place passes, a middle still displaced is
+    // given up (`dead`: reading that vector before it is rewritten is an error, not stale data).
+    struct Ws {
+        int on;             // the context is in scope and the knob is on
+        int nt, poison;     // LBFGS_WORK_SPLIT_NT; LBFGS_WORK_SPLIT=...poison
+        int lo, hi;         // the middle, in segments from the rank's first
+        double* alt;        // from the vector pool on first use
+        int alt_failed;     // ... which failed: the passes stay unsplit (counted)
+        const double* main;
+        int displaced;
+        const double* dead;
+    };
+    Ws ws;
 };
+
+// the default end window of a split work vector, in bytes of the vector per end: the tail of q / r
+// that a pass leaves in the Infinity Cache for the next one, walking the other way. Measured at
+// n = 1e8 (profiles/r08/work_split): 200 MB with the middle non-temporal cleared
+// DESIGN.md §7's rule on both boxes it ran on, so an unset LBFGS_WORK_SPLIT means that window.
+constexpr int64_t kWsWindowBytes = 200'000'000;
+constexpr int kWsDefaultOn = 1;
+// process-wide counters of the split work vector (lbfgs_kernels.hip; lbk_work_split_stats):
+// [0] split passes, [1] consolidation copies (ws_whole), [2] failed allocations of the alternate
+// buffer, [3] displaced middles given up
+extern "C" unsigned long long* lbk_ws_counters(void);
 
 #define LBK_UG_SLOT (LBK_NSLOTS - 4) /* scratch result slot of lbk_ug_materialise (no solver path uses it) */
 // fills the buffer of unstored gradient c->ug[i] (k_objective at its x; lbfgs_kernels.hip)
@@ -3138,11 +3257,24 @@ inline int ug_find(const lbk_ctx* c, const double* p) {
         if (c->ug[i].g && c->ug[i].g == p) return i;
     return -1;
 }
-inline int ug_in(lbk_ctx* c, const double* p) {
+// Split work vector, the entry points' side (defined below). ws_whole: p is about to be read by an
+// entry point that knows nothing of the split - a displaced middle is copied back first (counted);
+// ws_fresh: p is about to be written whole. Both ride ug_in / ug_out, which every entry point calls
+// for the vectors it touches; the split-aware entry points pass ws = false for the work vector they
+// handle themselves.
+inline int ws_whole(lbk_ctx* c, const double* p);
+inline int ws_whole_all(lbk_ctx* c);
+inline void ws_fresh(lbk_ctx* c, const double* p);
+
+inline int ug_in(lbk_ctx* c, const double* p, bool ws = true) {
+    if (ws && p)
+        if (const int rc = ws_whole(c, p)) return rc;
     const int i = p ? ug_find(c, p) : -1;
     return i >= 0 && !c->ug[i].stored ? lbk_ug_materialise(c, i) : 0;
 }
-inline int ug_out(lbk_ctx* c, std::initializer_list<const double*> w) {
+inline int ug_out(lbk_ctx* c, std::initializer_list<const double*> w, bool ws = true) {
+    for (const double* p : w)
+        if (ws && p) ws_fresh(c, p);
     for (auto& e : c->ug)
         for (const double* p : w)
             if (e.g && e.g == p) e.g = nullptr;
@@ -3162,6 +3294,7 @@ inline int ug_out(lbk_ctx* c, std::initializer_list<const double*> w) {
 // solve that made it - a later solve may write these buffers from outside the device layer (a
 // device-callback objective's gradient).
 inline int ug_flush(lbk_ctx* c) {
+    if (const int rc = ws_whole_all(c)) return rc;
     for (int i = 0; i < 2; ++i) {
         if (c->ug[i].g && !c->ug[i].stored) {
             const int rc = lbk_ug_materialise(c, i);
@@ -3190,6 +3323,88 @@ inline void ug_record(lbk_ctx* c, double* g, const double* x, int obj, int store
             return -2;                                                                       \
         }                                                                                    \
     } while (0)
+
+// ---- split work vector, host side (lbk_ctx::Ws) ----
+// the middle's elements (one rank: local = global)
+inline int64_t ws_elo(const lbk_ctx* c) { return (int64_t)c->ws.lo * c->geo.L; }
+inline int64_t ws_ehi(const lbk_ctx* c) { return std::min<int64_t>((int64_t)c->ws.hi * c->geo.L, c->geo.n_loc); }
+inline int ws_dead_error(lbk_ctx* c) {
+    snprintf(c->err, sizeof c->err, "split work vector: a vector whose displaced middle was given up is read");
+    return -1;
+}
+inline int ws_whole(lbk_ctx* c, const double* p) {
+    lbk_ctx::Ws& w = c->ws;
+    if (p == w.dead) return ws_dead_error(c);
+    if (p != w.main || !w.displaced) return 0;
+    const int64_t e0 = ws_elo(c), e1 = ws_ehi(c);
+    HIPCHK(c, hipMemcpyAsync(const_cast<double*>(w.main) + e0, w.alt + e0, sizeof(double) * (size_t)(e1 - e0),
+                             hipMemcpyDeviceToDevice, c->stream));
+    w.displaced = 0;
+    lbk_ws_counters()[1]++;
+    return 0;
+}
+inline int ws_whole_all(lbk_ctx* c) {
+    c->ws.dead = nullptr;  // (data from outside enters the vectors: a solve begins)
+    return c->ws.displaced ? ws_whole(c, c->ws.main) : 0;
+}
+inline void ws_fresh(lbk_ctx* c, const double* p) {
+    if (p == c->ws.main) c->ws.displaced = 0;
+    if (p == c->ws.dead) c->ws.dead = nullptr;
+}
+// A split-aware reader of v: where its middle lives (ws.min, range set), or nothing to select
+inline int ws_reader(lbk_ctx* c, const double* v, WSplit& ws) {
+    ws = WSplit{nullptr, nullptr, 0, 0};
+    if (v == c->ws.dead) return ws_dead_error(c);
+    if (v == c->ws.main && c->ws.displaced) ws = WSplit{c->ws.alt, nullptr, c->ws.lo, c->ws.hi};
+    return 0;
+}
+// An in-place pass over v: the middle's source and destination for this launch; the record toggles
+inline int ws_pass(lbk_ctx* c, double* v, WSplit& ws) {
+    lbk_ctx::Ws& w = c->ws;
+    ws = WSplit{nullptr, nullptr, 0, 0};
+    if (v == w.dead) return ws_dead_error(c);
+    if (!w.on || w.alt_failed) return 0;
+    if (!w.alt) {
+        w.alt = lbk_vec_alloc(c);
+        if (!w.alt) {
+            w.alt_failed = 1;
+            lbk_ws_counters()[2]++;
+            c->err[0] = 0;
+            (void)hipGetLastError();
+            return 0;
+        }
+    }
+    if (w.main != v) {
+        if (w.displaced) {  // the other vector's middle is in alt, which this pass overwrites
+            w.dead = w.main;
+            lbk_ws_counters()[3]++;
+        }
+        w.main = v;
+        w.displaced = 0;
+    }
+    ws = w.displaced ? WSplit{w.alt, v, w.lo, w.hi} : WSplit{v, w.alt, w.lo, w.hi};
+    w.displaced ^= 1;
+    lbk_ws_counters()[0]++;
+    return 0;
+}
+// LBFGS_WORK_SPLIT=...poison, after a split pass: the copy of the middle the pass read is stale
+inline int ws_poison(lbk_ctx* c, const WSplit& ws) {
+    if (!c->ws.poison || ws.lo >= ws.hi || !ws.mout) return 0;
+    const int64_t e0 = ws_elo(c), e1 = ws_ehi(c);
+    HIPCHK(c, hipMemsetAsync(const_cast<double*>(ws.min) + e0, 0xff, sizeof(double) * (size_t)(e1 - e0), c->stream));
+    return 0;
+}
+// the readers through DirArgs (TWOLOOP commit and trials)
+inline int ws_dir(lbk_ctx* c, DirArgs& da) {
+    WSplit ws;
+    if (const int rc = ws_reader(c, da.dsrc, ws)) return rc;
+    if (ws.min) {
+        da.dalt = ws.min;
+        da.alo = ws_elo(c);
+        da.ahi = ws_ehi(c);
+    }
+    return 0;
+}
 
 Geo kgeo(const lbk_ctx* c) {
     Geo g;

@@ -947,6 +947,19 @@ class Context:
         """vectors that asked for a physically contiguous allocation (LBFGS_VEC_ALLOC=contiguous) and got a plain one"""
         return int(lib().lbfgs_vector_fallbacks(self.h))
 
+    @staticmethod
+    def work_split_stats():
+        """the split work vector's process-wide counters (LBFGS_WORK_SPLIT; the device layer's
+        lbk_work_split_stats): dict(passes, copies, alloc_failed, given_up) - split passes launched,
+        consolidation copies of a displaced middle, failed allocations of the alternate buffer (the
+        context then stays unsplit), displaced middles given up when the other work vector took
+        the alternate buffer"""
+        out = (C.c_uint64 * 4)()
+        fn = lib().lbk_work_split_stats  # (bound here: an older library selected with LBFGS_LIB lacks it)
+        fn.argtypes, fn.restype = [C.POINTER(C.c_uint64)], None
+        fn(out)
+        return dict(passes=int(out[0]), copies=int(out[1]), alloc_failed=int(out[2]), given_up=int(out[3]))
+
     def wait_stats(self):
         """host waits on completion words: dict(slept_s, waits, adaptive) (lbfgs_wait_stats)"""
         s, w, a = C.c_double(), C.c_uint64(), C.c_int()
