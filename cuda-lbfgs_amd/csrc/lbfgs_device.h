@@ -241,7 +241,7 @@ typedef struct {
     unsigned long long chain_epoch;
 } lbk_spec;
 int lbk_small_spec_ok(const lbk_ctx* c, int h);
-/* small n, single rank: a line search (lbfgs_driver.c ls_*, LBFGS_LS_* numbering) continued on
+/* small n, single rank: a line search (lbfgs_search.h, LBFGS_LS_* numbering) continued on
  * the device from the top of one of its iterations, in one cooperative launch (k_coop_search),
  * d materialised. The state is the host loop's: its constants, the values the host already holds
  * (the commit's first trial, the backtracking commit's f at its next step, the last trial pass),

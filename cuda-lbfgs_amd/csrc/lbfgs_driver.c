@@ -1,7 +1,8 @@
 /* lbfgs_driver.c — C host driver of the MI355X L-BFGS solver (public ABI: include/lbfgs_hip.h).
  *
  * The control flow is the reference's LBFGS() (sequential-implementation/lbfgs.cpp:17-203) and
- * its line searches (line_search.cpp:8-189), restated over scalars only: every n-vector lives
+ * its line searches (line_search.cpp:8-189; their loops are lbfgs_search.h's, shared with the
+ * device), restated over scalars only: every n-vector lives
  * on the GPU and every vector operation is a fused device pass (lbfgs_kernels.hip). The host
  * sees, per iteration, one 512-byte read-back of the commit's reductions (g.d, f, s.y, y.y,
  * |g|^2, s.g, g.d_phi), plus one per extra line-search trial.
@@ -31,6 +32,7 @@
 
 #include "lbfgs_device.h"
 #include "lbfgs_hip.h"
+#include "lbfgs_search.h"
 
 /* roctx ranges (SURVEY §5 tracing): "lbfgs iteration" around every iteration and "line search"
  * around its trials, visible under rocprofv3 --marker-trace; no-ops without a tool attached.
@@ -102,8 +104,11 @@ struct lbfgs_ctx {
     int dmode, d_ready;
     double rho_last, a0;
     int ref_b_last, ref_a_last, s_last_pair;
-    int spec_valid;
-    double spec_f, spec_dphi, spec_tot[LBK_KMAX];
+    double spec_tot[LBK_KMAX];
+    /* this iteration's line search (lbfgs_search.h): its constants and loop variables, and the
+     * values it holds - the fused commit's first trial at a0 (have_spec), the backtracking
+     * commit's f at the next step (have_cand), the last trial pass (tc_*) */
+    lbk_search sr;
     int gt_valid;
     double gt_alpha;
     int unfused; /* LBFGS_FLAG_UNFUSED */
@@ -112,10 +117,6 @@ struct lbfgs_ctx {
      * a halving chain, or f and g.d together for the Wolfe searches; d stays unmaterialised for
      * the first two trial passes and the commit */
     int batch;
-    int cand_valid;
-    double cand_alpha, cand_f;
-    int tc_n, tc_dphi_ok;
-    double tc_a[LBK_TRIALS_NC], tc_f[LBK_TRIALS_NC], tc_dphi;
     int trial_passes;
     /* the last two-loop iteration whose search ran trial passes here took three or more of them
      * (tl_search: this iteration's search is such a one): the next one materialises d first */
@@ -820,24 +821,13 @@ static int materialize_d(lbfgs_ctx* c) {
  * g.d (:160) in the same read (the gradient is recomputed by the commit, never stored). Results
  * are those of separate single-step passes, bit for bit. */
 static int trial_batched(lbfgs_ctx* c, double alpha, int need_g, double* f, double* dphi) {
-    if (!need_g && c->cand_valid && alpha == c->cand_alpha) { /* reduced by the first commit */
-        *f = c->cand_f;
-        return 0;
-    }
-    for (int j = 0; j < c->tc_n; ++j)
-        if (alpha == c->tc_a[j] && (!need_g || (j == 0 && c->tc_dphi_ok))) {
-            *f = c->tc_f[j];
-            if (need_g && dphi) *dphi = c->tc_dphi;
-            return 0;
-        }
     const int want_dphi = need_g || c->ls == LBFGS_LS_WOLFE || c->ls == LBFGS_LS_BACKTRACKING_WOLFE;
     double a[LBK_TRIALS_NC];
     int nc = 1;
     a[0] = alpha;
     if (!want_dphi) {
-        const double ratio = c->ls == LBFGS_LS_BACKTRACKING ? c->K.backtracking_alpha : 0.5;
         nc = LBK_TRIALS_NC;
-        for (int j = 1; j < nc; ++j) a[j] = a[j - 1] * ratio;
+        lbk_search_chain(c->ls, &c->sr, alpha, a);
     }
     /* d: the buffer once materialised; -g formed on the fly (one rank); the last second-loop
      * update formed on the fly for this iteration's first two trial passes, then materialised
@@ -864,28 +854,19 @@ static int trial_batched(lbfgs_ctx* c, double alpha, int need_g, double* f, doub
     double t[LBK_TRIALS_NC + 1];
     DEVNC(lbk_fetch(c->dev, SLOT_TRIAL(c->m), nc + (want_dphi ? 1 : 0), t));
     c->trial_passes++;
-    c->tc_n = nc;
-    for (int j = 0; j < nc; ++j) {
-        c->tc_a[j] = a[j];
-        c->tc_f[j] = t[j];
-    }
-    c->tc_dphi_ok = want_dphi;
-    c->tc_dphi = want_dphi ? t[nc] : 0.0;
     *f = t[0];
-    if (need_g && dphi) *dphi = c->tc_dphi;
-    if (want_dphi)
+    if (want_dphi) {
+        lbk_search_note_fg(&c->sr, alpha, t);
+        *dphi = t[1];
         c->trials_fg++;
-    else
+    } else {
+        lbk_search_note_f(&c->sr, a, t);
         c->trials_f++;
+    }
     return 0;
 }
 
 static int trial(lbfgs_ctx* c, double alpha, int need_g, double* f, double* dphi) {
-    if (c->spec_valid && alpha == c->a0) {
-        *f = c->spec_f;
-        if (dphi) *dphi = c->spec_dphi;
-        return 0;
-    }
     if (c->vf && c->vf_cand_valid && !need_g) { /* f already reduced by the first commit pass */
         for (int j = 0; j < LBK_VF_NA; ++j)
             if (alpha == c->vf_cand[j]) {
@@ -893,6 +874,7 @@ static int trial(lbfgs_ctx* c, double alpha, int need_g, double* f, double* dphi
                 return 0;
             }
     }
+    if (lbk_search_lookup(&c->sr, alpha, need_g, f, dphi)) return 0;
     if (c->batch && !c->unfused && !ext_obj(c)) return trial_batched(c, alpha, need_g, f, dphi);
     int rc = materialize_d(c);
     if (rc) return rc;
@@ -906,7 +888,7 @@ static int trial(lbfgs_ctx* c, double alpha, int need_g, double* f, double* dphi
         if (need_g) {
             DEV(lbk_dot(c->dev, c->gt, c->d, SLOT_MISC(c->m) + 3));
             DEVNC(lbk_fetch(c->dev, SLOT_MISC(c->m) + 3, 1, &t[1]));
-            if (dphi) *dphi = t[1];
+            *dphi = t[1];
         }
     } else if (ext_obj(c)) {
         /* reference order: the backtracking-Wolfe search takes grad(x_new) before f(x_new)
@@ -925,14 +907,14 @@ static int trial(lbfgs_ctx* c, double alpha, int need_g, double* f, double* dphi
             double t;
             DEV(lbk_dot(c->dev, c->gt, c->d, SLOT_TRIAL(c->m)));
             DEVNC(lbk_fetch(c->dev, SLOT_TRIAL(c->m), 1, &t));
-            if (dphi) *dphi = t;
+            *dphi = t;
         }
     } else {
         double t[2];
         DEV(lbk_trial(c->dev, c->obj, c->x, c->d, alpha, need_g ? c->gt : NULL, SLOT_TRIAL(c->m)));
         DEVNC(lbk_fetch(c->dev, SLOT_TRIAL(c->m), 2, t));
         *f = t[0];
-        if (need_g && dphi) *dphi = t[1];
+        if (need_g) *dphi = t[1];
     }
     if (need_g)
         c->trials_fg++;
@@ -941,186 +923,26 @@ static int trial(lbfgs_ctx* c, double alpha, int need_g, double* f, double* dphi
     return 0;
 }
 
-static double cubic_interp(double a0, double a1, double p0, double dp0, double p1, double dp1) {
-    double d1 = dp0 + dp1 - 3 * (p1 - p0) / (a1 - a0); /* line_search.cpp:8-12 */
-    double d2 = copysign(sqrt(d1 * d1 - dp0 * dp1), a1 - a0);
-    return a0 + (a1 - a0) * (dp0 + d2 - d1) / (dp0 - dp1 + 2 * d2);
-}
-
-static double quad_interp(double a0, double p0, double dp0, double p1) { /* :14-16 */
-    return a0 - 0.5 * dp0 * a0 * a0 / (p1 - p0 - dp0 * a0);
-}
-
-static int search_here(const lbfgs_ctx* c, double alpha, int need_g);
-static int search_device(lbfgs_ctx* c, double gd, lbk_search* st);
-
-/* line_search.cpp:19-30 (f(x) == f_current, g.d == gd: identical values, evaluated once) */
-static int ls_backtracking(lbfgs_ctx* c, double gd, double* out) {
-    const lbfgs_constants* K = &c->K;
-    double alpha = K->initial_step;
-    for (;;) {
-        if (search_here(c, alpha, 0)) {
-            lbk_search st = {0};
-            st.alpha = alpha;
-            const int rc = search_device(c, gd, &st);
-            if (rc < 0) return rc;
-            if (rc == 0 && st.done) {
-                *out = st.step;
-                return 0;
-            }
-            if (rc == 0) alpha = st.alpha; /* its pass budget spent: on from there */
-        }
-        double fx, ft;
-        int rc = ls_fx(c, alpha, &fx); /* f(x) - f(x + alpha d), left operand first */
-        if (!rc) rc = trial(c, alpha, 0, &ft, NULL);
-        if (rc) return rc;
-        if (!(fx - ft < K->c1 * alpha * gd)) break;
-        alpha *= K->backtracking_alpha;
-        if (alpha < K->backtracking_tol) break;
-    }
-    *out = alpha;
-    return 0;
-}
-
-/* line_search.cpp:33-55 */
-static int ls_backtracking_wolfe(lbfgs_ctx* c, double gd, double* out) {
-    const lbfgs_constants* K = &c->K;
-    double alpha = K->initial_step;
-    for (;;) {
-        if (search_here(c, alpha, 1)) {
-            lbk_search st = {0};
-            st.alpha = alpha;
-            const int rd = search_device(c, gd, &st);
-            if (rd < 0) return rd;
-            if (rd == 0 && st.done) {
-                *out = st.step;
-                return 0;
-            }
-            if (rd == 0) alpha = st.alpha;
-        }
-        double fn, dphi, fx;
-        int rc = trial(c, alpha, 1, &fn, &dphi);
-        if (!rc) rc = ls_fx(c, 0.0, &fx);
-        if (rc) return rc;
-        if (fn > fx + K->c1 * alpha * gd) {
-            alpha *= K->backtracking_alpha;
-        } else if (dphi < K->c2 * gd) {
-            alpha *= 1.1;
-        } else {
-            break;
-        }
-        if (alpha < K->backtracking_tol) break;
-    }
-    *out = alpha;
-    return 0;
-}
-
-/* line_search.cpp:57-121 */
-static int ls_interpolation(lbfgs_ctx* c, double gd, double* out) {
-    const lbfgs_constants* K = &c->K;
-    double f_x;
-    int rc0 = ls_fx(c, K->initial_step, &f_x);
-    if (rc0) return rc0;
-    double alpha = K->initial_step, alpha_prev = 0.0, f_prev = f_x;
-    int it = 0;
-    for (;;) {
-        if (search_here(c, alpha, 0)) { /* it: the counter before the loop's `it++ < 20` test */
-            lbk_search st = {0};
-            st.alpha = alpha;
-            st.alpha_prev = alpha_prev;
-            st.f_prev = f_prev;
-            st.iter = it;
-            const int rd = search_device(c, gd, &st);
-            if (rd < 0) return rd;
-            if (rd == 0 && st.done) {
-                *out = st.step;
-                return 0;
-            }
-            if (rd == 0) {
-                alpha = st.alpha;
-                alpha_prev = st.alpha_prev;
-                f_prev = st.f_prev;
-                it = st.iter;
-            }
-        }
-        if (!(it++ < 20)) break;
-        double f_new;
-        int rc = trial(c, alpha, 0, &f_new, NULL);
-        if (rc) return rc;
-        if (f_new <= f_x + K->c1 * alpha * gd) {
-            *out = alpha;
-            return 0;
-        }
-        if (alpha < K->wolfe_interp_min) {
-            *out = K->wolfe_interp_min;
-            return 0;
-        }
-        if (alpha_prev > 0) {
-            double delta = alpha - alpha_prev;
-            if (fabs(delta) < 1e-10) {
-                alpha *= 0.5;
-            } else {
-                double ga = (f_new - f_x - gd * alpha) / (alpha * alpha);
-                alpha = cubic_interp(alpha_prev, alpha, f_prev, gd, f_new, ga);
-                if (alpha < 0.1 * alpha_prev || alpha > 0.9 * alpha_prev) alpha = alpha_prev * 0.5;
-            }
-        } else {
-            alpha = quad_interp(alpha, f_new, gd, f_x);
-            if (alpha < 0.1 * K->initial_step || alpha > 0.9 * K->initial_step)
-                alpha = K->initial_step * 0.5;
-        }
-        alpha_prev = alpha;
-        f_prev = f_new;
-    }
-    *out = alpha;
-    return 0;
-}
-
 /* Small n (single rank, a cooperative size, device objective): once a line search needs a trial
- * pass, the rest of the search runs on the device in one launch (lbk_search_dev: the same loop,
- * the same expressions, the same passes and caches) instead of a launch and a host
- * round trip per trial pass, and the commit at the step it finds follows in the same launch.
- * search_here: trial(alpha, need_g) would launch a pass, and the device form applies. */
+ * pass, the rest of the search runs on the device in one launch (lbk_search_dev: the same loop
+ * from the same text, lbfgs_search.h, so the same passes and caches) instead of a
+ * launch and a host round trip per trial pass, and the commit at the step it finds follows in the
+ * same launch. search_here: trial(alpha, need_g) would launch a pass, and the device form applies. */
 static int search_here(const lbfgs_ctx* c, double alpha, int need_g) {
+    double f, dphi;
     if (ext_obj(c) || c->unfused || !c->batch || c->vf || !lbk_search_dev_ok(c->dev, c->obj)) return 0;
-    if (c->spec_valid && alpha == c->a0) return 0; /* the commit's first trial: no pass */
-    if (!need_g && c->cand_valid && alpha == c->cand_alpha) return 0;
-    for (int j = 0; j < c->tc_n; ++j) /* the last trial pass */
-        if (alpha == c->tc_a[j] && (!need_g || (j == 0 && c->tc_dphi_ok))) return 0;
-    return 1;
+    return !lbk_search_lookup(&c->sr, alpha, need_g, &f, &dphi);
 }
 
-/* st: the caller's loop variables at the top of an iteration (alpha, and the search's own); the
- * constants and the host's caches are filled in here, and the caches come back as the host loop
- * would leave them. Returns 0 (st->done: the step; else the loop variables to go on from), 1 when
- * the launch's grid barrier timed out (nothing usable came back: the host loop goes on from the
- * same state, and the device form is off for the context), or < 0. */
-static int search_device(lbfgs_ctx* c, double gd, lbk_search* st) {
-    const lbfgs_constants* K = &c->K;
+/* c->sr at the top of an iteration of its loop goes to the device and comes back as the host loop
+ * would have left it. Returns 0 (sr.done: the step; else its pass budget is spent and the loop
+ * variables are those to go on from), 1 when the launch's grid barrier timed out (nothing came
+ * back: the host loop goes on from the same state, and the device form is off for the context),
+ * or < 0. */
+static int search_device(lbfgs_ctx* c) {
+    lbk_search* st = &c->sr;
     int rc = materialize_d(c);
     if (rc) return rc;
-    st->f_x = c->f_cur; /* ls_fx for a device objective */
-    st->gd = gd;
-    st->c1 = K->c1;
-    st->c2 = K->c2;
-    st->amin = K->wolfe_interp_min;
-    st->init = K->initial_step;
-    st->beta = K->backtracking_alpha;
-    st->tol = K->backtracking_tol;
-    st->have_spec = c->spec_valid;
-    st->spec_a = c->a0;
-    st->spec_f = c->spec_f;
-    st->spec_dphi = c->spec_dphi;
-    st->have_cand = c->cand_valid;
-    st->cand_a = c->cand_alpha;
-    st->cand_f = c->cand_f;
-    st->tc_n = c->tc_n;
-    st->tc_dphi_ok = c->tc_dphi_ok;
-    st->tc_dphi = c->tc_dphi;
-    for (int j = 0; j < LBK_TRIALS_NC; ++j) {
-        st->tc_a[j] = c->tc_a[j];
-        st->tc_f[j] = c->tc_f[j];
-    }
     lbk_search_commit cm = {c->g, c->xn, c->gn, c->S[c->free_pair], c->Y[c->free_pair], c->search_cslot};
     rc = lbk_search_dev(c->dev, c->obj, c->ls, c->x, c->d, st, &cm);
     if (rc == -6) { /* barrier time-out: the host loop takes over */
@@ -1133,13 +955,6 @@ static int search_device(lbfgs_ctx* c, double gd, lbk_search* st) {
     c->trials_fg += st->passes_fg;
     c->trial_passes += passes;
     c->passes += passes;
-    c->tc_n = st->tc_n;
-    c->tc_dphi_ok = st->tc_dphi_ok;
-    c->tc_dphi = st->tc_dphi;
-    for (int j = 0; j < LBK_TRIALS_NC; ++j) {
-        c->tc_a[j] = st->tc_a[j];
-        c->tc_f[j] = st->tc_f[j];
-    }
     c->search_launches++;
     if (st->committed) {
         c->search_committed = 1;
@@ -1149,88 +964,71 @@ static int search_device(lbfgs_ctx* c, double gd, lbk_search* st) {
     return 0;
 }
 
-/* line_search.cpp:125-189 */
-static int ls_wolfe(lbfgs_ctx* c, double gd, double* out) {
+/* the host's trial for the shared loops: stops the loop where the device form applies (not for
+ * the one trial after a launch that came back unfinished: that iteration runs here, as it would
+ * have without the device form). With LBFGS_FLAG_REFERENCE_CALLS it makes the reference's fresh
+ * f(x) calls in its order: before every backtracking trial (line_search.cpp:24, left operand
+ * first), after every backtracking-Wolfe trial (:42). */
+typedef struct {
+    lbfgs_ctx* c;
+    int on_host;
+} ls_host;
+
+static int host_trial(void* ctx, double alpha, int need_g, double* f, double* dphi) {
+    ls_host* h = (ls_host*)ctx;
+    lbfgs_ctx* c = h->c;
+    if (!h->on_host && search_here(c, alpha, need_g)) return 0;
+    h->on_host = 0;
+    int rc = 0;
+    if (c->ls == LBFGS_LS_BACKTRACKING) rc = ls_fx(c, alpha, &c->sr.f_x);
+    if (!rc) rc = trial(c, alpha, need_g, f, dphi);
+    if (!rc && c->ls == LBFGS_LS_BACKTRACKING_WOLFE) rc = ls_fx(c, 0.0, &c->sr.f_x);
+    return rc ? rc : 1; /* (errors are negative) */
+}
+
+/* line_search.cpp:19-189: the loops of lbfgs_search.h from their start values (f(x) == f_current,
+ * g.d == gd: identical values, evaluated once), over host_trial, continued on the device where
+ * that applies. After a launch that came back unfinished (its pass budget spent, or its grid
+ * barrier timed out) the loop resumes from c->sr with that iteration's trial on the host; only
+ * the next iteration may launch again. */
+static int search_run(lbfgs_ctx* c, double gd, double* out) {
     const lbfgs_constants* K = &c->K;
-    double f_x;
-    int rc0 = ls_fx(c, K->initial_step, &f_x);
-    if (rc0) return rc0;
-    double alpha = K->initial_step;
-    double alpha_lo = 0.0, alpha_hi = INFINITY, f_lo = f_x, dphi_lo = gd;
-    for (int iter = 0; iter < 20; ++iter) {
-        if (search_here(c, alpha, 0)) {
-            lbk_search st = {0};
-            st.alpha = alpha;
-            st.alpha_lo = alpha_lo;
-            st.alpha_hi = alpha_hi;
-            st.f_lo = f_lo;
-            st.dphi_lo = dphi_lo;
-            st.iter = iter;
-            const int rd = search_device(c, gd, &st);
-            if (rd < 0) return rd;
-            if (rd == 0 && st.done) {
-                *out = st.step;
-                return 0;
-            }
-            /* rd == 1: the device search gave up (a grid barrier timed out) having changed nothing;
-             * it is off for this context now, and this iteration of the host loop runs as it
-             * would have. rd == 0, not done (its pass budget spent; 20 passes cover the 20
-             * iterations, so not expected): on from its state */
-            if (rd == 0) {
-                alpha = st.alpha;
-                alpha_lo = st.alpha_lo;
-                alpha_hi = st.alpha_hi;
-                f_lo = st.f_lo;
-                dphi_lo = st.dphi_lo;
-                iter = st.iter;
-            }
-        }
-        double f_new, dphi_new;
-        /* f first; the gradient only if the sufficient-decrease tests pass (:144-153) */
-        int rc = trial(c, alpha, 0, &f_new, NULL);
+    lbk_search* s = &c->sr;
+    s->gd = gd;
+    s->c1 = K->c1;
+    s->c2 = K->c2;
+    s->amin = K->wolfe_interp_min;
+    s->init = K->initial_step;
+    s->beta = K->backtracking_alpha;
+    s->tol = K->backtracking_tol;
+    s->f_x = c->f_cur;
+    if (c->ls == LBFGS_LS_INTERPOLATION || c->ls == LBFGS_LS_WOLFE) { /* :65,133 */
+        const int rc = ls_fx(c, K->initial_step, &s->f_x);
         if (rc) return rc;
-        if (f_new > f_x + K->c1 * alpha * gd || (f_new >= f_lo && iter > 0)) {
-            alpha_hi = alpha;
-            alpha = cubic_interp(alpha_lo, alpha_hi, f_lo, dphi_lo, f_new,
-                                 (f_new - f_x - gd * alpha) / (alpha * alpha));
-            continue;
-        }
-        rc = trial(c, alpha, 1, &f_new, &dphi_new);
-        if (rc) return rc;
-        if (fabs(dphi_new) <= -K->c2 * gd) {
-            *out = alpha;
-            return 0;
-        }
-        if (dphi_new >= 0) {
-            alpha_hi = alpha;
-            alpha = cubic_interp(alpha_lo, alpha_hi, f_lo, dphi_lo, f_new, dphi_new);
-        } else {
-            alpha_lo = alpha;
-            f_lo = f_new;
-            dphi_lo = dphi_new;
-            if (alpha_hi == INFINITY)
-                alpha *= 2;
-            else
-                alpha = cubic_interp(alpha_lo, alpha_hi, f_lo, dphi_lo, f_new, dphi_new);
-        }
-        if (alpha < K->wolfe_interp_min) {
-            *out = K->wolfe_interp_min;
-            return 0;
-        }
     }
-    *out = alpha;
+    s->alpha = K->initial_step;
+    s->alpha_prev = s->alpha_lo = 0.0;
+    s->alpha_hi = INFINITY;
+    s->f_prev = s->f_lo = s->f_x;
+    s->dphi_lo = gd;
+    s->iter = 0;
+    s->done = s->committed = 0;
+    ls_host h = {c, 0};
+    while (!s->done) {
+        int rc = lbk_search_run(c->ls, s, host_trial, &h);
+        if (rc) return rc;
+        if (s->done) break;
+        rc = search_device(c); /* host_trial stopped the loop */
+        if (rc < 0) return rc;
+        h.on_host = 1;
+    }
+    *out = s->step;
     return 0;
 }
 
 static int run_line_search(lbfgs_ctx* c, double gd, double* alpha) {
     TRACE_PUSH("line search");
-    int rc;
-    switch (c->ls) {
-        case LBFGS_LS_BACKTRACKING: rc = ls_backtracking(c, gd, alpha); break;
-        case LBFGS_LS_INTERPOLATION: rc = ls_interpolation(c, gd, alpha); break;
-        case LBFGS_LS_WOLFE: rc = ls_wolfe(c, gd, alpha); break;
-        default: rc = ls_backtracking_wolfe(c, gd, alpha); break;
-    }
+    const int rc = search_run(c, gd, alpha);
     TRACE_POP();
     return rc;
 }
@@ -1311,9 +1109,9 @@ static int commit(lbfgs_ctx* c, int dmode, double alpha, int cslot, double* tot,
                        c->ref_a_last, alpha, c->xn, c->gn, c->S[pair], c->Y[pair], cslot, with_cand ? cand : 0.0));
         DEVNC(lbk_fetch(c->dev, cslot, with_cand ? 8 : 7, tot));
         if (with_cand) {
-            c->cand_valid = 1;
-            c->cand_alpha = cand;
-            c->cand_f = tot[LBK_C_FC];
+            c->sr.have_cand = 1;
+            c->sr.cand_a = cand;
+            c->sr.cand_f = tot[LBK_C_FC];
         }
     }
     c->commits++;
@@ -1512,9 +1310,9 @@ static int iterate(lbfgs_ctx* c) {
     c->cur_epoch = 0;
     c->cur_spec = 0;
     c->d_ready = 0;
-    c->spec_valid = 0;
-    c->cand_valid = 0;
-    c->tc_n = 0;
+    c->sr.have_spec = 0;
+    c->sr.have_cand = 0;
+    c->sr.tc_n = 0;
     if (c->tl_search && c->trial_passes > 0) c->many_passes = c->trial_passes >= 3;
     c->tl_search = 0;
     c->trial_passes = 0;
@@ -1665,9 +1463,9 @@ static int iterate(lbfgs_ctx* c) {
             if (rc) return rc;
             c->commits++;
             if (cand > 0.0) {
-                c->cand_valid = 1;
-                c->cand_alpha = cand;
-                c->cand_f = tot[LBK_C_FC];
+                c->sr.have_cand = 1;
+                c->sr.cand_a = cand;
+                c->sr.cand_f = tot[LBK_C_FC];
             }
         } else {
             rc = commit(c, c->dmode, c->a0, cslot, tot, cand);
@@ -1686,9 +1484,10 @@ static int iterate(lbfgs_ctx* c) {
             if (rc) return rc;
             gd = tot[LBK_C_GD];
         }
-        c->spec_valid = 1;
-        c->spec_f = tot[LBK_C_F];
-        c->spec_dphi = tot[LBK_C_DPHI];
+        c->sr.have_spec = 1;
+        c->sr.spec_a = c->a0;
+        c->sr.spec_f = tot[LBK_C_F];
+        c->sr.spec_dphi = tot[LBK_C_DPHI];
         memcpy(c->spec_tot, tot, sizeof tot);
     } else {
         rc = materialize_d(c);
@@ -1728,7 +1527,7 @@ static int iterate(lbfgs_ctx* c) {
             rc = spec_next(c, alpha);
             if (rc) return rc;
         }
-    } else if (!(c->spec_valid && alpha == c->a0) || c->recommit_a0) {
+    } else if (!(c->sr.have_spec && alpha == c->a0) || c->recommit_a0) {
         /* batched: d may still be unmaterialised (formed on the fly again, same bits) */
         if (!(c->batch && !c->unfused && !ext_obj(c) && !c->d_ready &&
               (c->dmode == LBK_D_TWOLOOP || (c->dmode == LBK_D_NEG_G && c->geo->world == 1)))) {
@@ -1897,8 +1696,8 @@ static int iterate_vf(lbfgs_ctx* c) {
     }
     c->dmode = D_VF;
     c->d_ready = 0;
-    c->cand_valid = 0;
-    c->tc_n = 0;
+    c->sr.have_cand = 0;
+    c->sr.tc_n = 0;
     c->trial_passes = 0;
     c->gt_valid = 0;
 
@@ -1917,9 +1716,10 @@ static int iterate_vf(lbfgs_ctx* c) {
     for (int j = 0; j < h; ++j) dgn = dgn + c->vf_cs[j] * T[gb + j];
     for (int j = 0; j < h; ++j) dgn = dgn + c->vf_cy[j] * T[gb + h + j];
     dgn = dgn + c->vf_cg * T[LBK_VF_GGO];
-    c->spec_valid = 1;
-    c->spec_f = T[LBK_VF_F];
-    c->spec_dphi = dgn;
+    c->sr.have_spec = 1;
+    c->sr.spec_a = c->a0;
+    c->sr.spec_f = T[LBK_VF_F];
+    c->sr.spec_dphi = dgn;
 
     double alpha = 0.0;
     rc = run_line_search(c, gd, &alpha);
@@ -2101,16 +1901,6 @@ static int cu_backtracking_wolfe(lbfgs_ctx* c, double gd, double* out) { /* :42-
     return 0;
 }
 
-static double cu_cubic(double a0, double a1, double p0, double dp0, double p1, double dp1) { /* :10-15 */
-    const double d1 = dp0 + dp1 - 3 * (p1 - p0) / (a1 - a0);
-    const double d2 = copysign(sqrt(d1 * d1 - dp0 * dp1), a1 - a0);
-    return a0 + (a1 - a0) * (dp0 + d2 - d1) / (dp0 - dp1 + 2 * d2);
-}
-
-static double cu_quad(double a0, double p0, double dp0, double p1) { /* :17-20 */
-    return a0 - 0.5 * dp0 * a0 * a0 / (p1 - p0 - dp0 * a0);
-}
-
 static int cu_interpolation(lbfgs_ctx* c, double gd, double* out) { /* :149-213 */
     const lbfgs_constants* K = &c->K;
     double f_x, alpha = K->initial_step, alpha_prev = 0.0, f_prev;
@@ -2134,11 +1924,11 @@ static int cu_interpolation(lbfgs_ctx* c, double gd, double* out) { /* :149-213 
                 alpha *= 0.5;
             } else {
                 const double ga = (f_new - f_x - gd * alpha) / (alpha * alpha);
-                alpha = cu_cubic(alpha_prev, alpha, f_prev, gd, f_new, ga);
+                alpha = lbk_search_cubic(alpha_prev, alpha, f_prev, gd, f_new, ga);
                 if (alpha < 0.1 * alpha_prev || alpha > 0.9 * alpha_prev) alpha = alpha_prev * 0.5;
             }
         } else {
-            alpha = cu_quad(alpha, f_new, gd, f_x);
+            alpha = lbk_search_quad(alpha, f_new, gd, f_x);
             if (alpha < 0.1 * K->initial_step || alpha > 0.9 * K->initial_step) alpha = K->initial_step * 0.5;
         }
         alpha_prev = alpha;
@@ -2261,12 +2051,12 @@ static int cv_interpolation(lbfgs_ctx* c, double gd, double* out, int* ok) { /* 
                 alpha *= 0.5;
             } else {
                 const double ga = (f_new - f_x - gd * alpha) / (alpha * alpha);
-                double next = cu_cubic(alpha_prev, alpha, f_prev, gd, f_new, ga);
+                double next = lbk_search_cubic(alpha_prev, alpha, f_prev, gd, f_new, ga);
                 if (next < 0.1 * alpha_prev || next > 0.9 * alpha_prev) next = alpha_prev * 0.5;
                 alpha = next;
             }
         } else {
-            double next = cu_quad(alpha, f_new, gd, f_x);
+            double next = lbk_search_quad(alpha, f_new, gd, f_x);
             if (next < 0.1 * K->initial_step || next > 0.9 * K->initial_step) next = K->initial_step * 0.5;
             alpha = next;
         }
@@ -2888,8 +2678,8 @@ int lbfgs_line_search(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int 
         const char* e = getenv("LBFGS_BATCH");
         if (e) c->batch = atoi(e) != 0;
     }
-    c->cand_valid = 0;
-    c->tc_n = 0;
+    c->sr.have_cand = 0;
+    c->sr.tc_n = 0;
     c->trial_passes = 0;
     c->many_passes = c->tl_search = 0;
     c->cuda = 0;
@@ -2920,18 +2710,12 @@ int lbfgs_line_search(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int 
     DEVNC(lbk_fetch(c->dev, SLOT_LAST(m), 1, &gd));
     c->dmode = LBK_D_BUF;
     c->d_ready = 1;
-    c->spec_valid = 0;
+    c->sr.have_spec = 0;
     c->search_cslot = -1;
     host_invalidate(c);
     c->hxx_valid = 0;
     double alpha = 0.0;
-    int rc;
-    switch (line_search) {
-        case LBFGS_LS_BACKTRACKING: rc = ls_backtracking(c, gd, &alpha); break;
-        case LBFGS_LS_INTERPOLATION: rc = ls_interpolation(c, gd, &alpha); break;
-        case LBFGS_LS_WOLFE: rc = ls_wolfe(c, gd, &alpha); break;
-        default: rc = ls_backtracking_wolfe(c, gd, &alpha); break;
-    }
+    const int rc = search_run(c, gd, &alpha);
     if (rc) return rc;
     *alpha_out = alpha;
     return 0;

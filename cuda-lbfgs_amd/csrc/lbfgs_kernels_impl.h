@@ -50,6 +50,7 @@
 #include <vector>
 
 #include "lbfgs_device.h"
+#include "lbfgs_search.h"
 #include "lbfgs_xgmi.h"
 
 #define LB_BLOCK 256
@@ -2420,17 +2421,18 @@ __global__ __launch_bounds__(LB_BLOCK) void k_coop_iter(SmallArgs a, Geo geo) {
 #undef SL
 
 // ---------------------------------------------------------------------------------------
-// Device-resident line searches for small n (lbfgs_driver.c ls_backtracking,
-// ls_interpolation, ls_wolfe, ls_backtracking_wolfe = line_search.cpp:19-30, 57-121, 125-189,
-// 33-55): once the host's search needs a trial pass, the rest of the search runs in ONE cooperative
-// launch - one workgroup per canonical segment, all resident, each trial a grid-wide pass of the
-// k_trials arithmetic (the f-only searches: f at the host's batched halving chain of
+// Device-resident line searches for small n (line_search.cpp:19-30, 57-121,
+// 125-189, 33-55): once the host's search needs a trial pass, the rest of the search runs in ONE
+// cooperative launch - one workgroup per canonical segment, all resident, each trial a grid-wide
+// pass of the k_trials arithmetic (the f-only searches: f at the batched halving chain of
 // LBK_TRIALS_NC steps; the Wolfe searches: f and g(x + a d) . d at one step) whose fixed-order
-// totals every workgroup forms (coop_pass), and the search's decisions restated on them in every
-// workgroup with the host's expressions (-ffp-contract=off on both sides; IEEE division and square
-// root), so all workgroups take the same branches and the step is the host's bit for bit. The
-// host's caches are restated too (the commit's first trial, the backtracking commit's f at the
-// next step, the last trial pass), so the launch evaluates exactly the passes the host loop would
+// totals every workgroup forms (coop_pass). The search itself is not restated here: its loops, its
+// interpolants, its caches (the commit's first trial, the backtracking commit's f at the next step,
+// the last trial pass) and a trial pass's bookkeeping are the one statement in lbfgs_search.h,
+// which this kernel instantiates over its grid-wide trial and the host driver (through
+// lbfgs_search_host.cpp) over its launch-per-pass trial, both with -ffp-contract=off, IEEE division
+// and square root. Every workgroup runs the loop on the same totals, so all take the same branches;
+// the step is the host's bit for bit, the launch evaluates exactly the passes the host loop would
 // and leaves the same cache behind. A search that ends at another step than the commit's first
 // trial is followed, in the same launch, by the commit at that step (the D_BUF commit of k_commit,
 // into the host-read commit slot): no second launch and no host round trip for the recommit.
@@ -2443,72 +2445,6 @@ struct SearchCommit {
     double* slot;   // device slot, or nullptr: no commit
     double* hslot;  // its host mirror (direct fetch), or nullptr
 };
-
-__device__ __forceinline__ double wolfe_cubic(double a0, double a1, double p0, double dp0, double p1, double dp1) {
-    const double d1 = dp0 + dp1 - 3 * (p1 - p0) / (a1 - a0);  // line_search.cpp:8-12
-    const double d2 = copysign(sqrt(d1 * d1 - dp0 * dp1), a1 - a0);
-    return a0 + (a1 - a0) * (dp0 + d2 - d1) / (dp0 - dp1 + 2 * d2);
-}
-__device__ __forceinline__ double search_quad(double a0, double p0, double dp0, double p1) {  // :14-16
-    return a0 - 0.5 * dp0 * a0 * a0 / (p1 - p0 - dp0 * a0);
-}
-
-// The searches themselves, shared by k_coop_search and the batched solver (k_batch_solve,
-// lbfgs_kernels_batch.hip): the host's caches, the bookkeeping of a trial pass, and the four loops
-// over a caller-supplied trial(alpha, need_g, f, dphi) -> bool (false: no value, the loop stops at
-// the top of its iteration with its variables in s).
-// lbfgs_driver.c trial() / trial_batched() for a device objective: the values the host holds
-__device__ __forceinline__ bool search_cached(const lbk_search& s, double alpha, bool need_g, double& f, double& dphi) {
-    if (s.have_spec && alpha == s.spec_a) {
-        f = s.spec_f;
-        dphi = s.spec_dphi;
-        return true;
-    }
-    if (!need_g && s.have_cand && alpha == s.cand_a) {
-        f = s.cand_f;
-        return true;
-    }
-    // (unrolled over the cache's capacity: a runtime-indexed tc_a[] would put the whole state in scratch)
-#pragma unroll
-    for (int j = 0; j < LBK_TRIALS_NC; ++j)
-        if (j < s.tc_n && alpha == s.tc_a[j] && (!need_g || (j == 0 && s.tc_dphi_ok))) {
-            f = s.tc_f[j];
-            dphi = s.tc_dphi;
-            return true;
-        }
-    return false;
-}
-// the steps of an f-only trial pass from alpha: the search's halving chain
-template <int LS>
-__device__ __forceinline__ void search_chain(const lbk_search& s, double alpha, double (&a)[LBK_TRIALS_NC]) {
-    const double ratio = LS == 0 ? s.beta : 0.5;
-    a[0] = alpha;
-#pragma unroll
-    for (int j = 1; j < LBK_TRIALS_NC; ++j) a[j] = a[j - 1] * ratio;
-}
-// a trial pass's totals become the last-trial-pass cache
-__device__ __forceinline__ void search_note_fg(lbk_search& s, double alpha, const double (&t)[2]) {
-    s.tc_n = 1;
-    s.tc_a[0] = alpha;
-    s.tc_f[0] = t[0];
-    s.tc_dphi = t[1];
-    s.tc_dphi_ok = 1;
-    s.passes_fg++;
-}
-__device__ __forceinline__ void search_note_f(lbk_search& s, const double (&a)[LBK_TRIALS_NC],
-                                              const double (&t)[LBK_TRIALS_NC]) {
-    s.tc_n = LBK_TRIALS_NC;
-#pragma unroll
-    for (int j = 0; j < LBK_TRIALS_NC; ++j) {
-        s.tc_a[j] = a[j];
-        s.tc_f[j] = t[j];
-    }
-    s.tc_dphi = 0.0;
-    s.tc_dphi_ok = 0;
-    s.passes_f++;
-}
-template <int LS, class Trial>
-__device__ __forceinline__ void search_loop(lbk_search& s, Trial&& trial);
 
 template <int OBJ, int LS>
 __global__ __launch_bounds__(LB_BLOCK) void k_coop_search(SmallArgs a, Geo geo, lbk_search s, const double* x,
@@ -2576,133 +2512,6 @@ __global__ __launch_bounds__(LB_BLOCK) void k_coop_search(SmallArgs a, Geo geo, 
             if (threadIdx.x == 0) __hip_atomic_store(a.done, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
-}
-
-// the four loops (s.alpha and the search's own variables: at the top of an iteration, in and out)
-template <int LS, class Trial>
-__device__ __forceinline__ void search_loop(lbk_search& s, Trial&& trial) {
-    auto finish = [&](double step) {
-        s.done = 1;
-        s.step = step;
-    };
-    double alpha = s.alpha;
-    if (LS == 0) {  // ls_backtracking
-        for (;;) {
-            double ft, dd;
-            if (!trial(alpha, false, ft, dd)) break;
-            if (!(s.f_x - ft < s.c1 * alpha * s.gd)) {
-                finish(alpha);
-                break;
-            }
-            alpha *= s.beta;
-            if (alpha < s.tol) {
-                finish(alpha);
-                break;
-            }
-        }
-    } else if (LS == 1) {  // ls_interpolation (iter: the loop counter before its `it++ < 20` test)
-        double alpha_prev = s.alpha_prev, f_prev = s.f_prev;
-        int it = s.iter;
-        for (;;) {
-            if (!(it++ < 20)) {
-                finish(alpha);
-                break;
-            }
-            double f_new, dd;
-            if (!trial(alpha, false, f_new, dd)) {
-                --it;
-                break;
-            }
-            if (f_new <= s.f_x + s.c1 * alpha * s.gd) {
-                finish(alpha);
-                break;
-            }
-            if (alpha < s.amin) {
-                finish(s.amin);
-                break;
-            }
-            if (alpha_prev > 0) {
-                const double delta = alpha - alpha_prev;
-                if (fabs(delta) < 1e-10) {
-                    alpha *= 0.5;
-                } else {
-                    const double ga = (f_new - s.f_x - s.gd * alpha) / (alpha * alpha);
-                    alpha = wolfe_cubic(alpha_prev, alpha, f_prev, s.gd, f_new, ga);
-                    if (alpha < 0.1 * alpha_prev || alpha > 0.9 * alpha_prev) alpha = alpha_prev * 0.5;
-                }
-            } else {
-                alpha = search_quad(alpha, f_new, s.gd, s.f_x);
-                if (alpha < 0.1 * s.init || alpha > 0.9 * s.init) alpha = s.init * 0.5;
-            }
-            alpha_prev = alpha;
-            f_prev = f_new;
-        }
-        s.alpha_prev = alpha_prev;
-        s.f_prev = f_prev;
-        s.iter = it;
-    } else if (LS == 2) {  // ls_wolfe
-        double lo = s.alpha_lo, hi = s.alpha_hi, f_lo = s.f_lo, dphi_lo = s.dphi_lo;
-        int iter = s.iter;
-        for (;;) {
-            if (iter >= 20) {
-                finish(alpha);
-                break;
-            }
-            double f_new, dphi_new;
-            if (!trial(alpha, false, f_new, dphi_new)) break;
-            if (f_new > s.f_x + s.c1 * alpha * s.gd || (f_new >= f_lo && iter > 0)) {
-                hi = alpha;
-                alpha = wolfe_cubic(lo, hi, f_lo, dphi_lo, f_new, (f_new - s.f_x - s.gd * alpha) / (alpha * alpha));
-                ++iter;
-                continue;
-            }
-            trial(alpha, true, f_new, dphi_new);  // the same pass's g.d (cached: want_dphi)
-            if (fabs(dphi_new) <= -s.c2 * s.gd) {
-                finish(alpha);
-                break;
-            }
-            if (dphi_new >= 0) {
-                hi = alpha;
-                alpha = wolfe_cubic(lo, hi, f_lo, dphi_lo, f_new, dphi_new);
-            } else {
-                lo = alpha;
-                f_lo = f_new;
-                dphi_lo = dphi_new;
-                if (hi == INFINITY)
-                    alpha *= 2;
-                else
-                    alpha = wolfe_cubic(lo, hi, f_lo, dphi_lo, f_new, dphi_new);
-            }
-            if (alpha < s.amin) {
-                finish(s.amin);
-                break;
-            }
-            ++iter;
-        }
-        s.alpha_lo = lo;
-        s.alpha_hi = hi;
-        s.f_lo = f_lo;
-        s.dphi_lo = dphi_lo;
-        s.iter = iter;
-    } else {  // ls_backtracking_wolfe
-        for (;;) {
-            double fn, dphi;
-            if (!trial(alpha, true, fn, dphi)) break;
-            if (fn > s.f_x + s.c1 * alpha * s.gd) {
-                alpha *= s.beta;
-            } else if (dphi < s.c2 * s.gd) {
-                alpha *= 1.1;
-            } else {
-                finish(alpha);
-                break;
-            }
-            if (alpha < s.tol) {
-                finish(alpha);
-                break;
-            }
-        }
-    }
-    s.alpha = alpha;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -150,7 +150,7 @@ static void device_objectives() {
                     EXPECT(mode == 3 || a + d == 0, "%s: speculative launches outside the speculative mode", tag);
                     adopted += a;
                     dropped += d;
-                    int64_t sl = 0, sc = 0;  // the device-resident line search (the double's restatement)
+                    int64_t sl = 0, sc = 0;  // the device-resident line search (on the double)
                     lbfgs_search_stats(c, &sl, &sc);
                     EXPECT(mode == 3 || mode == 4 || sl == 0, "%s: device searches outside the small-n forms", tag);
                     EXPECT(sc <= sl, "%s: %lld device-search commits of %lld launches", tag, (long long)sc,
@@ -338,6 +338,46 @@ static void api_surface() {
     EXPECT(lbfgs_ctx_create(&bad, 10, 0, 0) == LBFGS_ERR_BAD_ARG && !bad, "m = 0");
 }
 
+// A search longer than one launch's pass budget (LBK_SEARCH_PASSES = 20 trial passes): the driver
+// resumes the shared loop from the state the launch hands back, runs that iteration's trial on the
+// host and launches again from the next. Backtracking with factor 0.99 along -g from a random point
+// of Rosenbrock at n = 10 000 rejects 674 steps: 169 trial passes of 4 steps on the host loop; 9
+// launches of 20 passes with one host pass between two of them.
+static void search_resume() {
+    const int64_t n = 10000;
+    const auto x = x0_for(n, 17);
+    std::vector<double> g(n), d(n);
+    orc_grad(ORC_OBJ_ROSENBROCK, x.data(), n, g.data());
+    for (int64_t i = 0; i < n; ++i) d[i] = -g[i];
+    lbfgs_constants k;
+    lbfgs_constants_default(&k);
+    k.backtracking_alpha = 0.99;
+    double step[2] = {0.0, 0.0};
+    int64_t launches[2] = {0, 0};
+    for (int small = 0; small < 2; ++small) {
+        setenv("LBFGS_DOUBLE_SMALL", small ? "1" : "0", 1);
+        lbfgs_ctx* c = nullptr;
+        EXPECT(lbfgs_ctx_create(&c, n, 5, 0) == 0, "create");
+        if (!c) continue;
+        EXPECT(lbfgs_line_search(c, LBFGS_OBJ_ROSENBROCK, nullptr, LBFGS_LS_BACKTRACKING, &k, x.data(), d.data(),
+                                 g.data(), &step[small]) == 0,
+               "long backtracking search, small %d: %s", small, lbfgs_last_error(c));
+        int64_t commits = 0;
+        lbfgs_search_stats(c, &launches[small], &commits);
+        lbfgs_ctx_destroy(c);
+    }
+    setenv("LBFGS_DOUBLE_SMALL", "0", 1);
+    int rejected = 0;  // the host loop's step is initial_step * 0.99^rejected, formed as the search forms it
+    for (double a = k.initial_step; !same_bits(a, step[0]) && rejected < 4000; a *= k.backtracking_alpha) ++rejected;
+    const int passes = rejected / 4 + 1;
+    std::printf("long backtracking search: step %.17g after %d rejected steps, %d trial passes on the host loop; "
+                "%lld device launches\n", step[0], rejected, passes, (long long)launches[1]);
+    EXPECT(passes > 20, "the search fits one launch (%d passes): nothing resumes", passes);
+    EXPECT(same_bits(step[0], step[1]), "resumed device search: step %.17g vs the host loop's %.17g", step[1], step[0]);
+    EXPECT(launches[0] == 0 && launches[1] >= 2, "device launches %lld / %lld", (long long)launches[0],
+           (long long)launches[1]);
+}
+
 // the C++ drop-in: LBFGS() with the reference's own objectives and with a caller lambda
 static void cxx_dropin() {
     setenv("LBFGS_MODE", "default", 1);
@@ -381,6 +421,7 @@ int main() {
     host_callbacks();
     dense_objective();
     api_surface();
+    search_resume();
     cxx_dropin();
     if (g_fail) {
         std::fprintf(stderr, "%d failure(s)\n", g_fail);

@@ -5,7 +5,8 @@ Wolfe or backtracking-Wolfe (sequential-implementation/line_search.cpp:19-30, 57
 
 Against the host loop (LBFGS_DEV_SEARCH=0) every case must give the same trajectory bit for bit
 AND the same trial and commit counters (trial passes with f only, with f and g.d, commits): the
-launch restates the host's caches, so it evaluates exactly the trial passes the host loop would.
+launch runs the host's loop from the same text (csrc/lbfgs_search.h) on the host's caches, so it
+evaluates exactly the trial passes the host loop would.
 The one pass it may add is d's materialisation (the host loop forms d on the fly for an
 iteration's first two trial passes and its commit; the launch reads it from the buffer): at most
 one per launch. Against the oracle's canonical restatement the trajectory is bit-exact.
@@ -99,3 +100,27 @@ def test_standalone_line_search_on_the_device(monkeypatch):
                 g = c.objective("rosenbrock", x)[1]
                 steps.append(c.line_search("rosenbrock", ls, x, -g, g))
         assert np.array_equal(bits([steps[0]]), bits([steps[1]])), (ls, steps)
+
+
+def test_search_resumes_after_a_spent_pass_budget(monkeypatch):
+    """A launch covers at most LBK_SEARCH_PASSES = 20 trial passes (80 backtracking steps). With the
+    factor 0.99 the search along -g from this point rejects 674 steps, 169 trial passes on the host
+    loop (counted by the CPU job, tests/sanitize/san_main.cpp search_resume, on the same inputs): the
+    driver resumes the loop from the state each launch hands back, runs that iteration's trial
+    itself and launches again from the next one. The step is the host loop's bit for bit. (The
+    binding returns the step of a stand-alone search only, so the pass counters are not compared.)"""
+    n = 10_000  # 20 segments, one context
+    x = L.x0_uniform(n, 17, -2.0, 2.0)
+    k = L.constants()
+    k.backtracking_alpha = 0.99
+    steps, launches = [], []
+    for dev in (False, True):
+        monkeypatch.setenv("LBFGS_DEV_SEARCH", "1" if dev else "0")
+        with L.Context(n, 5) as c:
+            g = c.objective("rosenbrock", x)[1]
+            steps.append(c.line_search("rosenbrock", "backtracking", x, -g, g, consts=k))
+            launches.append(c.search_stats()[0])
+    print("steps", steps, "launches", launches)
+    assert np.array_equal(bits([steps[0]]), bits([steps[1]])), steps
+    assert launches[0] == 0
+    assert launches[1] >= 2, launches
