@@ -3,7 +3,9 @@
 // constants, tolerance and iteration limit and differ in x0, each solved by ONE workgroup that runs
 // the whole loop of iterate() (lbfgs_driver.c) on the device. A translation unit of its own: twelve
 // large kernels for the stencil objectives (k_batch_solve), and four for dense quadratics with each
-// problem's own A and b (k_batch_solve_dense, further down: the driver's external-objective path).
+// problem's own A and b (k_batch_solve_dense, further down: the driver's external-objective path),
+// and four for a caller's objective evaluated by the host between launches (k_batch_solve_ext, behind
+// the dense ones: the dense kernel with the evaluation taken out).
 //
 // The two kernel templates follow different branches of iterate() and stay two kernels. What the
 // branches have in common is written once, as force-inlined stages that both call (batch_enter,
@@ -34,6 +36,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 
 #define LBK_BATCH_NMAX 32768       // L = 512 and at most 64 segments: stage 2 is one wave
@@ -547,6 +550,54 @@ __global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_dense_ragged(BatchArgs
 #include "lbfgs_kernels_batch_solve_dense.h"
 }
 
+// ---------------------------------------------------------------------------------------
+// A caller's objective (lbfgs_batch_set_device_objective): k_batch_solve_ext is
+// the dense kernel with the evaluation taken out. A problem that needs f and the gradient at a point
+// writes the point into its Z row, stores where it stands (BatchExtRec, beside its BatchState) and is
+// left; the host calls the caller's function once for all waiting problems and launches again. The
+// kernel holds no wait, no flag and no time-out, as the other batch kernels.
+// ---------------------------------------------------------------------------------------
+enum { LBK_EXT_TOP = 0, LBK_EXT_AT_X0 = 1, LBK_EXT_SEARCH = 2, LBK_EXT_COMMIT_F = 3, LBK_EXT_COMMIT_G = 4 };
+
+// where a problem stands between two launches: its phase, the step it waits for, the search's
+// variables, the driver's three caches, the search's pass count and cap flag. d is in its buffer,
+// g . d in s.gd and the commit reads LBK_D_BUF, so nothing else has to survive.
+struct BatchExtRec {
+    int phase, wait, capped, passes;
+    long long evals;  // rounds the problem was active in
+    double pend;
+    DenseWave D;
+    lbk_search s;
+};
+
+struct BatchExtArgs {
+    double* zbase;     // element 0 of problem 0's point row Z; its gradient row GT one vector behind
+    const double* F;   // [B]: f at the pending point, from the round
+    int* active;       // [B]: set for a problem that waits (cleared by the host before the launch)
+    int* nactive;      // how many were set
+    BatchExtRec* rec;  // [B]
+    long long* evals;  // [B]: rec[p].evals as the problem was last left, for the host's read-back
+};
+
+struct BatchExtLds {
+    BatchLds L;
+    BatchExtRec xr[4];
+};
+
+template <int LS>
+__global__ __launch_bounds__(LB_BLOCK) void k_batch_solve_ext(BatchArgs a, BatchExtArgs xa, Geo geo_b) {
+#include "lbfgs_kernels_batch_solve_ext.h"
+}
+
+const void* batch_ext_kernel(int ls) {
+    switch (ls) {
+        case 0: return (const void*)k_batch_solve_ext<0>;
+        case 1: return (const void*)k_batch_solve_ext<1>;
+        case 2: return (const void*)k_batch_solve_ext<2>;
+        default: return (const void*)k_batch_solve_ext<3>;
+    }
+}
+
 // A ragged batch has its own kernels, with the BatchRagged as their last argument; a uniform batch
 // runs the kernels it always ran.
 const void* batch_dense_kernel(int ls, bool ragged) {
@@ -608,6 +659,17 @@ struct lbfgs_batch {
     const double* ref_A;
     const double* ref_b;
     int64_t ref_astride, ref_lda, ref_ldb;
+    // a caller's objective (lbfgs_batch_set_device_objective): per problem the point row Z and the
+    // gradient row GT in the vectors' own layout, f per problem, the flags (running, the count of
+    // waiting problems, then active[B]) and the resumable records; allocated by the first setter call
+    lbfgs_batch_device_fn cb;
+    bool cb_set;
+    double* cb_x;
+    double* cb_F;
+    int* cb_flags;
+    BatchExtRec* cb_rec;
+    long long* cb_evals;
+    std::vector<long long> hevals;  // the rounds each problem was active in, after the last such solve
     hipStream_t stream;
     std::vector<BatchState> hst;  // the states after the last solve
     std::vector<double> htr;      // its traces (LBFGS_FLAG_TRACE)
@@ -759,6 +821,11 @@ void lbfgs_batch_destroy(lbfgs_batch* b) {
     if (b->dq_A) (void)hipFree(b->dq_A);
     if (b->dq_b) (void)hipFree(b->dq_b);
     if (b->dq_x) (void)hipFree(b->dq_x);
+    if (b->cb_x) (void)hipFree(b->cb_x);
+    if (b->cb_F) (void)hipFree(b->cb_F);
+    if (b->cb_flags) (void)hipFree(b->cb_flags);
+    if (b->cb_rec) (void)hipFree(b->cb_rec);
+    if (b->cb_evals) (void)hipFree(b->cb_evals);
     if (b->tab) (void)hipFree(b->tab);
     if (b->order) (void)hipFree(b->order);
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -970,7 +1037,107 @@ int lbfgs_batch_set_dense_quadratics_device(lbfgs_batch* b, const double* A_dev,
     return 0;
 }
 
+int lbfgs_batch_set_device_objective(lbfgs_batch* b, const lbfgs_batch_device_fn* fn) {
+    if (!b) return LBFGS_ERR_BAD_ARG;
+    b->err[0] = 0;
+    if (!fn) {  // cleared; the buffers stay for a later call
+        b->cb_set = false;
+        b->cb.eval = nullptr;
+        return 0;
+    }
+    const char* bad = nullptr;
+    if (b->ragged)
+        bad = "a uniform batch (problems of one size), not a ragged one";
+    else if (!fn->eval)
+        bad = "eval";
+    else if (fn->flags != 0)
+        bad = "flags 0";
+    if (bad) {  // the objective set before, if any, stays as it is
+        snprintf(b->err, sizeof b->err, "lbfgs_batch_set_device_objective: %s", bad);
+        return LBFGS_ERR_BAD_ARG;
+    }
+    if (!b->cb_rec) {
+        BHIP(b, hipSetDevice(b->device));
+        const size_t B = (size_t)b->B, xbytes = sizeof(double) * 2 * (size_t)batch_sum_v(b);
+        double *x = nullptr, *F = nullptr;
+        int* fl = nullptr;
+        BatchExtRec* rec = nullptr;
+        long long* ev = nullptr;
+        // ghost cells and padding of Z and GT are zero and stay zero, as the batch's other vectors'
+        if (hipMalloc((void**)&x, xbytes) != hipSuccess || hipMalloc((void**)&F, sizeof(double) * B) != hipSuccess ||
+            hipMalloc((void**)&fl, sizeof(int) * (B + 2)) != hipSuccess ||
+            hipMalloc((void**)&rec, sizeof(BatchExtRec) * B) != hipSuccess ||
+            hipMalloc((void**)&ev, sizeof(long long) * B) != hipSuccess ||
+            hipMemsetAsync(x, 0, xbytes, b->stream) != hipSuccess ||
+            hipMemsetAsync(F, 0, sizeof(double) * B, b->stream) != hipSuccess ||
+            hipMemsetAsync(rec, 0, sizeof(BatchExtRec) * B, b->stream) != hipSuccess ||
+            hipMemsetAsync(ev, 0, sizeof(long long) * B, b->stream) != hipSuccess ||
+            hipStreamSynchronize(b->stream) != hipSuccess) {  // the batch stays usable for its other objectives
+            (void)hipGetLastError();
+            if (x) (void)hipFree(x);
+            if (F) (void)hipFree(F);
+            if (fl) (void)hipFree(fl);
+            if (rec) (void)hipFree(rec);
+            if (ev) (void)hipFree(ev);
+            snprintf(b->err, sizeof b->err, "lbfgs_batch_set_device_objective: out of device memory");
+            return LBFGS_ERR_NOMEM;
+        }
+        b->cb_x = x;
+        b->cb_F = F;
+        b->cb_flags = fl;
+        b->cb_rec = rec;
+        b->cb_evals = ev;
+    }
+    b->cb = *fn;
+    b->cb_set = true;
+    return 0;
+}
+
 }  // extern "C"
+
+// The rounds of a solve with the caller's objective: launch, synchronise, one call of eval for all
+// waiting problems, launch again, until no problem waits (then none is running: a launch leaves a
+// problem waiting or finished). The rounds are bounded by what the searches can ask for.
+static int batch_ext_rounds(lbfgs_batch* b, const char* who, BatchArgs& a, const BatchExtArgs& xa, const void* kern,
+                            int grid, void** kargs, int max_iterations, long long* launches) {
+    // an iteration's evaluations: its search's trials (20 of interpolation and Wolfe, 4096 of
+    // backtracking-Wolfe here, backtracking's own count of steps down to its tolerance where that
+    // is more) and the commit's two; the solve's: those of max_iterations iterations, and x0's
+    double per_iter = (double)LBK_BATCH_BTW_CAP;
+    if (a.K.backtracking_alpha > 0 && a.K.backtracking_alpha < 1 && a.K.backtracking_tol > 0 && a.K.initial_step > 0)
+        per_iter = std::max(per_iter, std::ceil(std::log(a.K.backtracking_tol / a.K.initial_step) /
+                                                std::log(a.K.backtracking_alpha)) + 1.0);
+    const double bound = 1.0 + ((double)max_iterations + 1.0) * (per_iter + 2.0);
+    const long long max_rounds = bound < 9e18 ? (long long)bound : LLONG_MAX;
+    const int64_t ld = 2 * b->vstride;
+    for (;;) {
+        int flags[2] = {0, 0};  // running, waiting
+        BHIP(b, hipMemsetAsync(b->cb_flags, 0, sizeof(int) * ((size_t)b->B + 2), b->stream));
+        BHIP(b, hipLaunchKernel(kern, dim3(grid), dim3(LB_BLOCK), kargs, 0, b->stream));
+        BHIP(b, hipMemcpyAsync(flags, b->cb_flags, sizeof flags, hipMemcpyDeviceToHost, b->stream));
+        BHIP(b, hipStreamSynchronize(b->stream));  // eval's ordering: everything that formed Z is complete
+        a.init = 0;
+        ++*launches;
+        if (flags[1] == 0) {
+            if (flags[0]) {  // cannot happen: a running problem waits
+                snprintf(b->err, sizeof b->err, "%s: problems running but none waiting", who);
+                return LBFGS_ERR_STATE;
+            }
+            return 0;
+        }
+        if (*launches > max_rounds) {
+            snprintf(b->err, sizeof b->err, "%s: problems unfinished after %lld rounds", who, *launches);
+            return LBFGS_ERR_STATE;
+        }
+        const int rc = b->cb.eval(xa.zbase, ld, b->cb_F, xa.zbase + b->vstride, ld, xa.active, flags[1], b->B, b->n,
+                                  b->cb.user);
+        BHIP(b, hipSetDevice(b->device));  // the callback may have left another device current
+        if (rc != 0) {
+            snprintf(b->err, sizeof b->err, "%s: device objective callback returned %d", who, rc);
+            return LBFGS_ERR_CALLBACK;
+        }
+    }
+}
 
 // Both forms of lbfgs_batch_minimize: x0 is read at xin + p * ldxin and x written at xout + p * ldxout,
 // device memory both. x0_host / x_out_host (the host form only) are copied to and from the batch's
@@ -979,11 +1146,13 @@ static int batch_solve(lbfgs_batch* b, const char* who, int objective, int line_
                        const double* xin, int64_t ldxin, double* xout, int64_t ldxout, const double* x0_host,
                        double* x_out_host, int max_iterations, double tolerance, unsigned flags, lbfgs_result* out) {
     const bool dense = objective == LBFGS_OBJ_DENSE_QUAD && b->dq_set;
-    if ((!dense && (objective < LBFGS_OBJ_ROSENBROCK || objective > LBFGS_OBJ_QUAD_SEPARABLE)) ||
+    const bool ext = objective == LBFGS_OBJ_DEVICE && b->cb_set && b->cb.eval && !b->ragged;
+    if ((!dense && !ext && (objective < LBFGS_OBJ_ROSENBROCK || objective > LBFGS_OBJ_QUAD_SEPARABLE)) ||
         line_search < LBFGS_LS_BACKTRACKING || line_search > LBFGS_LS_BACKTRACKING_WOLFE || max_iterations < 0 ||
         (flags & ~(LBFGS_FLAG_TRACE | LBFGS_FLAG_QUIET)) != 0) {
         snprintf(b->err, sizeof b->err, "%s: device stencil objectives (the dense quadratic once "
-                 "its data is set), the four line searches, LBFGS_FLAG_TRACE / LBFGS_FLAG_QUIET only", who);
+                 "its data is set, LBFGS_OBJ_DEVICE once lbfgs_batch_set_device_objective has set one), the four "
+                 "line searches, LBFGS_FLAG_TRACE / LBFGS_FLAG_QUIET only", who);
         return LBFGS_ERR_BAD_ARG;
     }
     const auto t0 = std::chrono::steady_clock::now();
@@ -1032,13 +1201,26 @@ static int batch_solve(lbfgs_batch* b, const char* who, int objective, int line_
         dq.ldb = b->dq_ref ? b->ref_ldb : b->n;
         if (b->ragged && !b->dq_ref) dq.astride = dq.lda = dq.ldb = LBFGS_BATCH_PACKED;  // the batch's own copies
     }
+    BatchExtArgs xa;
+    memset(&xa, 0, sizeof xa);
+    if (ext) {
+        xa.zbase = b->cb_x + LBK_FRONT;
+        xa.F = b->cb_F;
+        xa.nactive = b->cb_flags + 1;
+        xa.active = b->cb_flags + 2;
+        xa.rec = b->cb_rec;
+        xa.evals = b->cb_evals;
+        a.running = b->cb_flags;  // running and the count of waiting problems come back in one copy
+    }
     BatchRagged rg = {b->tab, nullptr};
     // the one kernel of this solve and its arguments
-    const void* const kern = dense ? batch_dense_kernel(line_search, b->ragged)
-                                   : batch_kernel(objective, line_search, b->ragged);
+    const void* const kern = ext     ? batch_ext_kernel(line_search)
+                             : dense ? batch_dense_kernel(line_search, b->ragged)
+                                     : batch_kernel(objective, line_search, b->ragged);
     void* args_stencil[] = {&a, &b->geo, &rg};     // rg: the ragged kernels' last argument; a uniform batch's
     void* args_dense[] = {&a, &dq, &b->geo, &rg};  // kernels have none, and the entry is not read
-    void** const kargs = dense ? args_dense : args_stencil;
+    void* args_ext[] = {&a, &xa, &b->geo};
+    void** const kargs = ext ? args_ext : dense ? args_dense : args_stencil;
     int grid = b->max_wg;
     if (grid <= 0) {  // every workgroup resident: occupancy x CUs
         int per_cu = 0;
@@ -1048,31 +1230,43 @@ static int batch_solve(lbfgs_batch* b, const char* who, int objective, int line_
     grid = std::min(grid, b->B);
     // the order of work balances workgroups that take several problems each; with one problem each
     // there is nothing to balance, and the problems stay where their index puts them
+    // (the table's order, of ragged batches: the kernels of a uniform batch, k_batch_solve_ext among
+    // them, have no such argument and take their problems by index)
     if (grid < b->B) rg.order = b->order;
     auto launch = [&] { return hipLaunchKernel(kern, dim3(grid), dim3(LB_BLOCK), kargs, 0, b->stream); };
     // x0 up (one contiguous copy; each workgroup moves its problem's x0 into the vector layout)
     if (x0_host)
         BHIP(b, hipMemcpyAsync(b->xio, x0_host, sizeof(double) * (size_t)batch_sum_n(b), hipMemcpyHostToDevice,
                                b->stream));
-    // every launch takes each unfinished problem at least one iteration further, or ends it
-    const long long max_launches = (long long)max_iterations / a.iters + 2;
     long long launches = 0;
-    for (;;) {
-        int running = 0;
-        BHIP(b, hipMemsetAsync(b->running, 0, sizeof(int), b->stream));
-        BHIP(b, launch());
-        BHIP(b, hipMemcpyAsync(&running, b->running, sizeof(int), hipMemcpyDeviceToHost, b->stream));
-        BHIP(b, hipStreamSynchronize(b->stream));
-        a.init = 0;
-        ++launches;
-        if (!running) break;
-        if (launches >= max_launches) {
-            snprintf(b->err, sizeof b->err, "%s: problems unfinished after %lld launches", who, launches);
-            return LBFGS_ERR_STATE;
+    if (ext) {
+        const int rc = batch_ext_rounds(b, who, a, xa, kern, grid, kargs, max_iterations, &launches);
+        if (rc != 0) return rc;
+    } else {
+        // every launch takes each unfinished problem at least one iteration further, or ends it
+        const long long max_launches = (long long)max_iterations / a.iters + 2;
+        for (;;) {
+            int running = 0;
+            BHIP(b, hipMemsetAsync(b->running, 0, sizeof(int), b->stream));
+            BHIP(b, launch());
+            BHIP(b, hipMemcpyAsync(&running, b->running, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+            BHIP(b, hipStreamSynchronize(b->stream));
+            a.init = 0;
+            ++launches;
+            if (!running) break;
+            if (launches >= max_launches) {
+                snprintf(b->err, sizeof b->err, "%s: problems unfinished after %lld launches", who, launches);
+                return LBFGS_ERR_STATE;
+            }
         }
     }
     b->hst.resize((size_t)b->B);
     BHIP(b, hipMemcpyAsync(b->hst.data(), b->st, sizeof(BatchState) * (size_t)b->B, hipMemcpyDeviceToHost, b->stream));
+    if (ext) {  // the rounds each problem was active in
+        b->hevals.resize((size_t)b->B);
+        BHIP(b, hipMemcpyAsync(b->hevals.data(), b->cb_evals, sizeof(long long) * (size_t)b->B, hipMemcpyDeviceToHost,
+                               b->stream));
+    }
     if (x_out_host)
         BHIP(b, hipMemcpyAsync(x_out_host, b->xio, sizeof(double) * (size_t)batch_sum_n(b), hipMemcpyDeviceToHost,
                                b->stream));
@@ -1102,6 +1296,7 @@ static int batch_solve(lbfgs_batch* b, const char* who, int objective, int line_
             r.seconds = secs;
             r.h_min = s.h_min;
             r.h_max = s.h_min < 0 ? -1 : s.h_max;
+            if (ext) r.f_calls = r.grad_calls = b->hevals[(size_t)p];
         }
     return 0;
 }

@@ -76,6 +76,16 @@ class DeviceFn(C.Structure):
     _fields_ = [("eval", DEVICE_EVAL), ("user", C.c_void_p), ("flags", C.c_uint)]
 
 
+# int eval(const double* z_dev, int64_t ldz, double* f_dev, double* g_dev, int64_t ldg, const int* active_dev,
+#          int n_active, int batch, int64_t n, void* user)
+BATCH_DEVICE_EVAL = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                C.c_int, C.c_int64, C.c_void_p)
+
+
+class BatchDeviceFn(C.Structure):
+    _fields_ = [("eval", BATCH_DEVICE_EVAL), ("user", C.c_void_p), ("flags", C.c_uint)]
+
+
 _lib = None
 
 
@@ -173,6 +183,7 @@ def lib():
     L.lbfgs_batch_ragged_plan.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.lbfgs_batch_create_ragged.argtypes = [C.POINTER(vp), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int]
     L.lbfgs_batch_sizes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.lbfgs_batch_set_device_objective.argtypes = [vp, C.POINTER(BatchDeviceFn)]
     L.lbfgs_set_device_objective.argtypes = [vp, C.POINTER(DeviceFn)]
     L.lbfgs_minimize_device.argtypes = [vp, C.c_int, C.POINTER(HostFn), C.c_int, C.POINTER(Constants),
                                         vp, vp, C.c_int, C.c_double, C.c_uint, C.POINTER(Result)]
@@ -203,7 +214,7 @@ EXPORTED_SYMBOLS = [
     "lbfgs_batch_set_launch", "lbfgs_batch_minimize", "lbfgs_batch_trace_len", "lbfgs_batch_trace_get",
     "lbfgs_batch_events_get", "lbfgs_batch_dense_plan", "lbfgs_batch_set_dense_quadratics",
     "lbfgs_batch_minimize_device", "lbfgs_batch_set_dense_quadratics_device",
-    "lbfgs_batch_ragged_plan", "lbfgs_batch_create_ragged", "lbfgs_batch_sizes",
+    "lbfgs_batch_ragged_plan", "lbfgs_batch_create_ragged", "lbfgs_batch_sizes", "lbfgs_batch_set_device_objective",
     "lbfgs_set_device_objective", "lbfgs_minimize_device", "lbfgs_solver_init_device", "lbfgs_get_x_device",
     "lbfgs_reducer_create", "lbfgs_reducer_destroy", "lbfgs_reducer_dot",
 ]
@@ -371,6 +382,7 @@ class Batch:
     def __init__(self, n, m, batch=None, device=0):
         self.m, self.device = int(m), int(device)
         self._dq_refs = None  # the tensors set_dense_quadratics_device refers to
+        self._dev_cb, self._dev_exc = None, None  # set_device_objective's callback, and what it raised
         if isinstance(n, np.ndarray) and n.ndim == 0:
             n = n.item()  # a 0-d array is one size
         self.ragged = not np.isscalar(n)
@@ -400,6 +412,7 @@ class Batch:
             lib().lbfgs_batch_destroy(self.h)
             self.h = None
         self._dq_refs = None
+        self._dev_cb = None
 
     def __enter__(self):
         return self
@@ -414,6 +427,9 @@ class Batch:
             pass
 
     def _err(self, what, rc):
+        exc, self._dev_exc = self._dev_exc, None
+        if exc is not None:  # the device callback raised: the library saw a nonzero return
+            raise exc
         msg = lib().lbfgs_batch_last_error(self.h)
         e = LbfgsError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
         e.rc = rc
@@ -425,6 +441,53 @@ class Batch:
         rc = lib().lbfgs_batch_set_launch(self.h, int(max_workgroups), int(iters_per_launch))
         if rc != 0:
             self._err("lbfgs_batch_set_launch", rc)
+
+    def set_device_objective(self, fn):
+        """The "device" objective of the whole batch: fn(Z, active) -> (F, G), called once per round for
+        every problem that waits for an evaluation. Z is a float64 CUDA tensor of shape (batch, n), a
+        zero-copy view of the batch's point rows (row stride > n), valid during the call and read-only
+        by contract; active a (batch,) int32 view, nonzero for the rows to evaluate. F of shape (batch,)
+        and G of shape (batch, n) are CUDA float64; what they hold for inactive rows is ignored (such a
+        row of Z holds the last point that problem was evaluated at). The glue copies F and G into
+        views of the batch's own rows, [0, n) of each, and then synchronises the stream that is current
+        when fn has returned. Every problem's result is bit for bit what Context.set_device_objective(
+        eager_grad=True) + Context.minimize_device("device") gives for it alone with the same f and g;
+        f_calls / grad_calls are the rounds the problem was active in. Uniform batches only. An
+        exception raised by fn ends the solve and is re-raised by minimize. fn = None clears."""
+        if fn is None:
+            rc = lib().lbfgs_batch_set_device_objective(self.h, None)
+            self._dev_cb = None
+            if rc != 0:
+                self._err("lbfgs_batch_set_device_objective", rc)
+            return
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+
+        def rows(ptr, ld, B, n, typestr="<f8"):
+            flat = torch.as_tensor(_DeviceView(ptr, (B - 1) * ld + n, typestr), device=dev)
+            return flat.as_strided((B, n), (ld, 1))
+
+        def ev(zp, ldz, fp, gp, ldg, ap, n_active, B, n, user):
+            try:
+                with torch.cuda.device(dev):
+                    Z = rows(zp, ldz, B, n)
+                    active = torch.as_tensor(_DeviceView(ap, B, "<i4"), device=dev)
+                    F, G = fn(Z, active)
+                    torch.as_tensor(_DeviceView(fp, B), device=dev).copy_(
+                        torch.as_tensor(F, dtype=torch.float64, device=dev).reshape(B))
+                    rows(gp, ldg, B, n).copy_(torch.as_tensor(G, dtype=torch.float64, device=dev).reshape(B, n))
+                    torch.cuda.current_stream(dev).synchronize()
+                return 0
+            except BaseException as e:  # never unwinds through the C frames
+                self._dev_exc = e
+                return 1
+
+        cb = BATCH_DEVICE_EVAL(ev)
+        fnc = BatchDeviceFn(cb, None, 0)
+        rc = lib().lbfgs_batch_set_device_objective(self.h, C.byref(fnc))
+        if rc != 0:
+            self._err("lbfgs_batch_set_device_objective", rc)
+        self._dev_cb = cb
 
     def set_dense_quadratics(self, A, b):
         """Data of objective "dense", problem p minimising x'A[p]x + b[p]'x: A of shape (batch, n, n), or
@@ -595,6 +658,7 @@ class Batch:
         k = consts if consts is not None else constants()
         fl = FLAG_QUIET | (FLAG_TRACE if trace else 0) | int(flags)
         obj = OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        self._dev_exc = None
         rc = lib().lbfgs_batch_minimize_device(self.h, obj, LINE_SEARCHES[line_search], C.byref(k), X0.data_ptr(),
                                                int(ldx0), X.data_ptr(), int(ldx), int(max_iterations), float(tolerance),
                                                fl, res)
@@ -626,6 +690,7 @@ class Batch:
         k = consts if consts is not None else constants()
         fl = FLAG_QUIET | (FLAG_TRACE if trace else 0) | int(flags)
         obj = OBJECTIVES[objective] if isinstance(objective, str) else int(objective)
+        self._dev_exc = None
         rc = lib().lbfgs_batch_minimize(self.h, obj, LINE_SEARCHES[line_search], C.byref(k), X0, X,
                                         int(max_iterations), float(tolerance), fl, res)
         if rc < 0:
@@ -641,7 +706,8 @@ class Batch:
                  status=[STATUS.get(int(s), int(s)) for s in code], status_code=code,
                  commits=col("commits", np.int64), trials_f=col("trials_f", np.int64),
                  trials_fg=col("trials_fg", np.int64), h_min=col("h_min", np.int64), h_max=col("h_max", np.int64),
-                 bytes=col("bytes", np.float64), launches=int(res[0].passes), seconds=float(res[0].seconds))
+                 bytes=col("bytes", np.float64), f_calls=col("f_calls", np.int64),
+                 grad_calls=col("grad_calls", np.int64), launches=int(res[0].passes), seconds=float(res[0].seconds))
         if trace:
             d["tr_f"], d["tr_gnorm"], d["tr_alpha"], d["events"] = [], [], [], []
             for p in range(self.batch):
@@ -674,9 +740,9 @@ class _DeviceView:
     """n float64 at a device address, for torch.as_tensor(view, device=...): a zero-copy tensor over
     memory the library owns (torch takes no ownership; the view is valid while the library says so)."""
 
-    def __init__(self, ptr, n):
+    def __init__(self, ptr, n, typestr="<f8"):
         # torch accepts writable views only; a read-only buffer (the callback's x) is one by contract
-        self.__cuda_array_interface__ = dict(shape=(int(n),), typestr="<f8", data=(int(ptr), False), version=2,
+        self.__cuda_array_interface__ = dict(shape=(int(n),), typestr=typestr, data=(int(ptr), False), version=2,
                                              strides=None)
 
 

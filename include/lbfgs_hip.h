@@ -496,6 +496,44 @@ int lbfgs_batch_create_ragged(lbfgs_batch** out, const int64_t* n, int m, int ba
  * may be NULL. A uniform batch reports n and p*n. */
 int lbfgs_batch_sizes(const lbfgs_batch* b, int64_t* n_out, int64_t* offset_out);
 
+/* A caller's own objective for the whole batch: after
+ * lbfgs_batch_set_device_objective both forms of lbfgs_batch_minimize take objective = LBFGS_OBJ_DEVICE.
+ * The solve runs in rounds: a launch takes every unfinished problem to the next point it needs f and
+ * the gradient at (or to its end), then ONE call of eval serves all waiting problems, then the next
+ * launch. Every problem's x, f, |g|, iterations, status, trials_f, trials_fg, commits, h_min / h_max,
+ * events and trace are bit for bit what lbfgs_set_device_objective(LBFGS_DEVICE_EAGER_GRAD) +
+ * lbfgs_minimize_device(LBFGS_OBJ_DEVICE) gives for that problem alone with a callback that computes
+ * the same f and g for that row. f_calls = grad_calls = the rounds the problem was active in (the
+ * single path's count, except at a step that is not a number, which that path evaluates again and
+ * this one does not); passes = kernel launches of the call; bytes = 8 n times the vectors the kernel
+ * streams: its passes as the other batch kernels count them, 3 per point formed and 2 per copy of x0
+ * or of a gradient, nothing of what the callback itself reads or writes.
+ * Limits: 1 <= n <= 32768, 1 <= m <= 16, uniform batches only (a ragged batch is refused with
+ * LBFGS_ERR_BAD_ARG and a message), the same flags and the 4096-trial cap of backtracking_wolfe. Of
+ * lbfgs_batch_set_launch the workgroup count applies; iterations per launch has no meaning here, since
+ * every iteration needs an evaluation. A solve whose rounds exceed what max_iterations and the
+ * searches' own bounds allow ends with LBFGS_ERR_STATE.
+ *
+ * One call evaluates every waiting problem of the batch. All pointers are device memory owned by the
+ * batch, valid during the call. Row p of z is z_dev + p*ldz: n doubles, read-only.
+ * For each p with active_dev[p] != 0, store f(z_p) to f_dev[p] and grad f(z_p) to g_dev + p*ldg, [0, n) only.
+ * Nothing outside [0, n) of a row of g_dev may be written.
+ * What the callback stores for other rows is ignored. Their z rows hold the last point that problem
+ * was evaluated at.
+ * n_active = how many rows are active (> 0). Return 0; anything else ends the call with
+ * LBFGS_ERR_CALLBACK, and the batch stays usable.
+ * Ordering is as lbfgs_device_eval: the batch's stream is synchronised before the call, and the
+ * callback's own work is complete when it returns. */
+typedef int (*lbfgs_batch_device_eval)(const double* z_dev, int64_t ldz, double* f_dev, double* g_dev, int64_t ldg,
+                                       const int* active_dev, int n_active, int batch, int64_t n, void* user);
+typedef struct { lbfgs_batch_device_eval eval; void* user; unsigned flags; /* 0 */ } lbfgs_batch_device_fn;
+/* NULL clears. Refused with LBFGS_ERR_BAD_ARG: a null eval, flags other than 0, a ragged batch; without
+ * an objective set LBFGS_OBJ_DEVICE stays LBFGS_ERR_BAD_ARG before anything is launched. The first call
+ * allocates two more vectors per problem (the point row and the gradient row) and a few hundred bytes
+ * per problem of state; LBFGS_ERR_NOMEM leaves the batch usable for its other objectives, which setting
+ * or clearing this one never disturbs. */
+int lbfgs_batch_set_device_objective(lbfgs_batch* b, const lbfgs_batch_device_fn* fn); /* NULL clears */
+
 /* ---- canonical reductions on caller-owned device buffers -------------------------------- */
 /* For objectives evaluated on the device (LBFGS_OBJ_DEVICE): the sum of their per-element terms in
  * the solver's canonical fixed order, so that f is reproducible run to run and
