@@ -26,7 +26,12 @@ Context.minimize_device("device"), both computed once per case and shared.
 5. real device math: torch objectives per row, f through Reducer.sum, from minimize and from
    minimize_device on rows at storage offset 1, and on a non-default torch stream;
 6. the guard inputs of tests/test_gpu_batch.py: event counts and statuses against the oracle's lines;
-7. refusals, a failing callback, a Python exception, clearing, and the batch's other objectives.
+7. refusals, a failing callback, a Python exception, clearing, and the batch's other objectives;
+8. a history of 16 pairs, the most a batch accepts, and of 8, filled and rotated (tests/hist_cases.py),
+   which also runs the single-problem LBFGS_OBJ_DEVICE reference at m = 16;
+9. the size limit, n = 32768;
+10. line-search constants that are not the defaults (tests/consts_cases.py, path 12), and one row
+    alone in a search of hundreds of rounds (backtracking_alpha = 0.99) beside two finished rows.
 """
 import ctypes as C
 import os
@@ -38,6 +43,8 @@ import torch  # noqa: F401  before lbfgs_amd loads liblbfgs_hip.so: one HIP runt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cuda-lbfgs_amd"))
+import consts_cases as K  # noqa: E402
+import hist_cases as HC  # noqa: E402
 import lbfgs_amd as L  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import test_gpu_batch as S  # noqa: E402  (same_bits, check_problem, message_counts, GUARD_BATCHES)
@@ -66,9 +73,7 @@ def host(t):
     return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
 
 
-def x0_batch(n):
-    return np.stack([O.x0_uniform(n, 1, -2.0, 2.0), 1e-3 * O.x0_uniform(n, 2, -2.0, 2.0),
-                     O.x0_uniform(n, 3, 1.0 - 1e-4, 1.0 + 1e-4), O.x0_uniform(n, 4, -2.0, 2.0)])
+x0_batch = HC.x0_batch  # (the four starts; the CPU condition tests need them without torch)
 
 
 class BatchLog:
@@ -94,16 +99,26 @@ class BatchLog:
 _reference = {}
 
 
-def reference(obj, ls, n, m, X0, maxit, tol, key):
-    """(oracle runs, single-problem runs) of a batch, computed once per key and shared (left unchanged)"""
+def device_constants(consts):
+    """lbfgs_constants with the fields of a dictionary replaced (None: the defaults)"""
+    k = L.constants()
+    for name, v in (consts or {}).items():
+        setattr(k, name, v)
+    return k
+
+
+def reference(obj, ls, n, m, X0, maxit, tol, key, consts=None):
+    """(oracle runs, single-problem runs) of a batch, computed once per key and shared (left unchanged).
+    consts: a dictionary of line-search constants that replace the defaults in both."""
     if key not in _reference:
         orc, one = [], []
         with L.Context(n, m) as c:
             for x0 in X0:
                 lo = H.Log(obj)
-                orc.append(O.lbfgs("host", x0, ls, m, maxit, tol, mode=O.CANON, f=lo.f, grad=lo.grad))
+                with np.errstate(all="ignore"):
+                    orc.append(O.lbfgs("host", x0, ls, m, maxit, tol, mode=O.CANON, f=lo.f, grad=lo.grad, consts=consts))
                 c.set_device_objective(DV.DeviceLog(obj), eager_grad=True)
-                r = c.minimize_device("device", dev(x0), ls, maxit, tol, trace=True)
+                r = c.minimize_device("device", dev(x0), ls, maxit, tol, trace=True, consts=device_constants(consts))
                 r["x"] = host(r["x"])
                 one.append(r)
         _reference[key] = (orc, one)
@@ -462,3 +477,87 @@ def test_other_objectives_of_the_batch_are_undisturbed():
         same(b.minimize("device", X0, "wolfe", max_iterations=iters, trace=True), dv0, "device again")
         b.set_device_objective(None)
         same(b.minimize("dense", X0, "wolfe", max_iterations=iters, trace=True), dq0, "dense after clearing")
+
+
+# ---- 8. a history of 16 pairs, and of 8 (tests/hist_cases.py) -----------------------------------------
+@pytest.mark.parametrize("case", HC.STENCIL, ids=HC.case_id)
+def test_long_history(case):
+    """m = 16, the largest history a batch accepts, and m = 8, on inputs that fill the ring and rotate it
+    (tests/test_history_inputs.py asserts that on the CPU, with the objective as callables): the oracle,
+    and the single-problem LBFGS_OBJ_DEVICE path at the same m."""
+    obj, n, m, ls, tol, differ = case
+    X0 = HC.stencil_x0(case)
+    orc, one = reference(obj, ls, n, m, X0, HC.MAXIT, tol, ("hist",) + case)
+    fn = BatchLog(obj)
+    with L.Batch(n, m, len(X0)) as b:
+        b.set_device_objective(fn)
+        res = b.minimize("device", X0, ls, max_iterations=HC.MAXIT, tolerance=tol, trace=True)
+    check_batch(res, orc, one, case)
+    check_rounds(fn, res)
+    HC.check_h_max(res, orc, m, case)
+    assert all(one[p]["h_max"] == m for p in range(len(X0)) if HC.full_ring(orc[p], m))
+    assert not differ or len(set(res["iterations"])) >= 2
+
+
+# ---- 9. the size limit ---------------------------------------------------------------------------------
+def test_size_limit():
+    """n = 32768, the largest a batch accepts: 64 segments, every lane of the stage-2 wave live"""
+    obj, ls, n, m, maxit = "rosenbrock", "backtracking", 32768, 3, 6
+    assert O.geometry(n) == (512, 64)
+    X0 = S.seeds_x0(n, [1, 2], -2.0, 2.0)
+    orc, one = reference(obj, ls, n, m, X0, maxit, 1e-5, ("limit",))
+    assert all(o["iters"] == maxit for o in orc)
+    fn = BatchLog(obj)
+    with L.Batch(n, m, len(X0)) as b:
+        b.set_device_objective(fn)
+        res = b.minimize("device", X0, ls, max_iterations=maxit, tolerance=1e-5, trace=True)
+    check_batch(res, orc, one, "n=32768")
+    check_rounds(fn, res)
+    assert list(res["h_max"]) == [m, m]
+
+
+# ---- 10. line-search constants that are not the defaults (tests/consts_cases.py, path 12) -------------
+@pytest.mark.parametrize("case", K.BATCH_CALLBACK, ids=lambda c: "-".join(str(v) for v in c))
+def test_varied_constants(case):
+    """A search here is an lbk_search record stored between launches and resumed: constants that are no
+    powers of two tell a stored step from a recomputed one. tests/test_constants_inputs.py asserts on the
+    CPU that the constants bite in every batch and what each reaches (failed searches beside problems
+    that run on, Wolfe expanding every iteration, backtracking-Wolfe growing a step some 24 times in every search)."""
+    ks, obj, n, m, ls, iters = case
+    X0 = K.batch_x0(n)
+    orc, one = reference(obj, ls, n, m, X0, iters, K.TOL, ("consts",) + case, consts=K.SETS[ks])
+    fn = BatchLog(obj)
+    with L.Batch(n, m, len(X0)) as b:
+        b.set_device_objective(fn)
+        res = b.minimize("device", X0, ls, max_iterations=iters, tolerance=K.TOL, consts=device_constants(K.SETS[ks]),
+                         trace=True)
+    print(f"{case}: {len(fn.rounds)} rounds, f_calls {list(res['f_calls'])}")
+    check_batch(res, orc, one, case)
+    check_rounds(fn, res)
+    assert res["launches"] == len(fn.rounds) + 1
+
+
+def test_one_row_alone_in_a_long_search():
+    """backtracking_alpha = 0.99: the middle row's first search rejects hundreds of steps, a round each,
+    while the rows beside it, done after their first evaluation, stay inactive: the record alone carries
+    the search from launch to launch. Its step and x against the single-problem path and the oracle."""
+    c = K.LONG_SEARCH
+    obj, ls, n, m, iters, row = c["objective"], c["search"], c["n"], c["m"], c["iterations"], c["row"]
+    X0 = K.long_search_x0()
+    orc, one = reference(obj, ls, n, m, X0, iters, K.TOL, ("long search",), consts=c["consts"])
+    fn = BatchLog(obj)
+    with L.Batch(n, m, len(X0)) as b:
+        b.set_device_objective(fn)
+        res = b.minimize("device", X0, ls, max_iterations=iters, tolerance=K.TOL, consts=device_constants(c["consts"]),
+                         trace=True)
+    print(f"long search: {len(fn.rounds)} rounds, f_calls {list(res['f_calls'])}")
+    check_batch(res, orc, one, "long search")
+    check_rounds(fn, res)
+    others = [p for p in range(len(X0)) if p != row]
+    step = res["tr_alpha"][row][0]
+    assert same_bits([step], [orc[row]["alpha"][0]]) and same_bits([step], [one[row]["tr_alpha"][0]])
+    assert same_bits(host(res["x"][row]), orc[row]["x"]) and same_bits(host(res["x"][row]), one[row]["x"])
+    assert all(res["f_calls"][p] == 1 and res["iterations"][p] == 0 and res["status"][p] == "converged" for p in others)
+    alone = fn.rounds[1:]
+    assert len(alone) >= c["rejected_at_least"] and res["f_calls"][row] == len(fn.rounds)
+    assert all(r[row] and not any(r[p] for p in others) for r in alone)

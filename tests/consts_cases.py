@@ -2,9 +2,11 @@
 
 One table, imported by the fixture generator (tests/golden/make_consts.py), the oracle pin
 (test_oracle_consts.py), the input conditions (test_constants_inputs.py) and the GPU parity
-tests (test_gpu_constants.py). The defaults (c1 1e-4, c2 0.9, initial_step 1, backtracking_alpha
-0.5, backtracking_tol 1e-8, wolfe_interp_min 1e-10) are powers of two where it matters, which
-hides "multiply again" against "multiply the stored value" and 1.0 written for initial_step.
+tests (test_gpu_constants.py: paths 1-10 and 13; devobj_gpu_cases.py: path 11, the device-callback
+objective; batchcb_gpu_cases.py: path 12, the batched callback). The defaults (c1 1e-4, c2 0.9,
+initial_step 1, backtracking_alpha 0.5, backtracking_tol 1e-8, wolfe_interp_min 1e-10) are powers
+of two where it matters, which hides "multiply again" against "multiply the stored value" and 1.0
+written for initial_step.
 
   K1  a ratio that is no power of two, strict c1: backtracking chains up to 0.7^19
   K2  a first step above 1 that is never accepted on the tridiagonal quadratic; Wolfe expands
@@ -85,6 +87,66 @@ LS_N, LS_SEED = 5000, 3
 LINE_SEARCH = [(ks, ls) for ks in ("K1", "K2", "K5") for ls in SEARCHES]
 # path 10, two emulated ranks, every rank owning segments
 SHARDED = ("K2", "quad_tridiag", 2_100_001, 5, "wolfe", 10)
+# path 11, the single-problem device-callback objective (LBFGS_OBJ_DEVICE), with and without
+# eager_grad: the HOST list's shape, compared with the host-callback path too
+DEVICE_OBJ = [(ks, "rosenbrock", 1000, 5, ls, 20) for ks in ("K1", "K2", "K5") for ls in SEARCHES]
+# path 12, the batched callback (k_batch_solve_ext: a search is an lbk_search record stored between
+# launches and resumed), four problems from batch_x0. K1 / K5 + Wolfe on Rosenbrock fail their
+# search at iteration 1 for three of the four starts and the fourth runs on; K2 + Wolfe on the
+# tridiagonal quadratic expands every iteration.
+BATCH_CALLBACK = [(ks, "quad_tridiag" if ks == "K2" else "rosenbrock", n, m, ls, 12)
+                  for ks in ("K1", "K2", "K5") for ls in SEARCHES for n in (5, 513) for m in (1, 5)]
+BATCH_CALLBACK += [
+    ("K3", "rosenbrock", 513, 5, "backtracking_wolfe", 12),  # grows the step by 1.1 some 24 times per search
+    ("K3", "quad_tridiag", 513, 5, "backtracking", 12),
+    ("K3", "rosenbrock", 513, 5, "wolfe", 12),               # problems that end inside their first search
+    ("K4", "rosenbrock", 513, 5, "backtracking", 12),        # initial_step < 1e-10: fails at once
+]
+# the resumable record alone: backtracking_alpha = 0.99 (tests/test_gpu_device_search.py's constant).
+# One row rejects hundreds of steps in its first search, a round each, beside two rows that start
+# within 1e-10 of Rosenbrock's minimiser and are done after their first evaluation.
+LONG_SEARCH = dict(objective="rosenbrock", n=513, m=3, search="backtracking", iterations=2, row=1,
+                   consts=dict(backtracking_alpha=0.99), rejected_at_least=300)
+# path 13, ragged batches. Stencil: sizes [513, 5, 1537, 129], problem p from x0 seed 1 + p; dense:
+# sizes [10, 100, 10] of the known-answer data, problems q = 0, 1, 3 of the dense_problem recipe
+RAGGED_SIZES = (513, 5, 1537, 129)
+RAGGED_DENSE_SIZES, RAGGED_DENSE_Q = (10, 100, 10), (0, 1, 3)
+BATCH_RAGGED = [(ks, "quad_tridiag" if ks == "K2" else "rosenbrock", RAGGED_SIZES, m, ls, 12)
+                for ks in ("K1", "K2", "K5") for ls in SEARCHES for m in (1, 5)]
+BATCH_RAGGED_DENSE = [(ks, "dense", RAGGED_DENSE_SIZES, m, ls, 40)
+                      for ks in ("K1", "K2", "K5") for ls in SEARCHES for m in (1, 5)]
+
+
+def batch_x0(n):
+    """the four starts of the batched callback's tests (hist_cases.x0_batch): two in [-2, 2], one of
+    those scaled by 1e-3, one within 1e-4 of the all-ones point"""
+    import hist_cases
+
+    return hist_cases.x0_batch(n)
+
+
+def long_search_x0():
+    import numpy as np
+
+    import oracle_lib as O
+
+    n = LONG_SEARCH["n"]
+    X0 = np.stack([O.x0_uniform(n, 5, 1.0 - 1e-10, 1.0 + 1e-10), O.x0_uniform(n, 17, LO, HI),
+                   O.x0_uniform(n, 6, 1.0 - 1e-10, 1.0 + 1e-10)])
+    return X0
+
+
+def ragged_id(case):
+    return "-".join("x".join(str(n) for n in v) if isinstance(v, tuple) else str(v) for v in case)
+
+
+def ragged_problems(case):
+    """the problems of a BATCH_RAGGED or BATCH_RAGGED_DENSE case, each as a uniform case of its own
+    size with the keyword arguments of oracle() that select it"""
+    ks, obj, sizes, m, ls, iters = case
+    if obj == "dense":
+        return [((ks, obj, n, m, ls, iters), dict(seed=10 + q, dense_q=q)) for n, q in zip(sizes, RAGGED_DENSE_Q)]
+    return [((ks, obj, n, m, ls, iters), dict(seed=1 + p)) for p, n in enumerate(sizes)]
 
 
 _runs = {}

@@ -4,7 +4,8 @@
 Device-callback objectives (LBFGS_OBJ_DEVICE), device-resident x0 / x, and the canonical
 reductions on caller-owned buffers (lbfgs_reducer_*). Everything compares bits.
 
-1. the device callback against the oracle and against the host-callback path, call counts included;
+1. the device callback against the oracle and against the host-callback path, call counts included,
+   also with line-search constants that are not the defaults (tests/consts_cases.py, path 11);
 2. real device math: torch objectives reduced through Reducer.sum, LBFGS_OBJ_DEVICE against the same
    torch function through LBFGS_OBJ_HOST;
 3. minimize_device / init_device / get_x_device against the host-buffer forms, on slices at storage
@@ -23,6 +24,7 @@ import torch  # noqa: F401  before lbfgs_amd loads liblbfgs_hip.so: one HIP runt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cuda-lbfgs_amd"))
+import consts_cases as K  # noqa: E402
 import lbfgs_amd as L  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import test_gpu_host_callbacks as H  # noqa: E402  (its CASES and its Log callables)
@@ -110,6 +112,45 @@ def test_device_callback_vs_oracle_and_host_path(obj, n, m, ls, iters):
             else:
                 assert r["f_calls"] == rh["f_calls"] and r["grad_calls"] == rh["grad_calls"]
                 assert r["grad_calls"] == sum(1 for k in d.calls if k[0])
+
+
+# ---- 1b. line-search constants that are not the defaults (tests/consts_cases.py, path 11) --------
+_host_runs = {}
+
+
+def host_run(case):
+    """the host-callback path's run of a case with its set's constants, computed once and shared"""
+    if case not in _host_runs:
+        ks, obj, n, m, ls, iters = case
+        lh = H.Log(obj)
+        with L.Context(n, m) as c:
+            _host_runs[case] = c.minimize("host", K.oracle(case, host=True)["x0"], ls, iters, tolerance=K.TOL, f=lh.f,
+                                          grad=lh.grad, trace=True, consts=K.device_constants(L, ks))
+    return _host_runs[case]
+
+
+@pytest.mark.parametrize("eager", [False, True], ids=["lazy", "eager"])
+@pytest.mark.parametrize("case", K.DEVICE_OBJ, ids=lambda c: "-".join(str(v) for v in c))
+def test_device_callback_with_varied_constants(case, eager):
+    """K1 / K2 / K5 x the four searches through LBFGS_OBJ_DEVICE: the oracle's bits with the same
+    constants, and the host-callback path's (tests/test_constants_inputs.py asserts on the CPU that
+    the constants bite in these inputs)"""
+    ks, obj, n, m, ls, iters = case
+    o, rh = K.oracle(case, host=True), host_run(case)
+    d = DeviceLog(obj)
+    with L.Context(n, m) as c:
+        c.set_device_objective(d, eager_grad=eager)
+        r = c.minimize_device("device", dev(o["x0"]), ls, iters, K.TOL, trace=True, consts=K.device_constants(L, ks))
+    assert np.array_equal(bits(host(r["x"])), bits(o["x"]))
+    assert np.array_equal(bits(r["tr_f"]), bits(o["f"])) and np.array_equal(bits(r["tr_gnorm"]), bits(o["gnorm"]))
+    assert same_alpha(r["tr_alpha"], o["alpha"])
+    assert r["iterations"] == o["iters"] and r["status"] == o["status"] and r["messages"] == o["messages"]
+    same_run(r, rh)
+    assert len(d.calls) > 0 and r["f_calls"] == rh["f_calls"]
+    if eager:
+        assert all(k[0] for k in d.calls) and r["grad_calls"] == len(d.calls)
+    else:
+        assert r["grad_calls"] == rh["grad_calls"] == sum(1 for k in d.calls if k[0])
 
 
 # ---- 2. real device math -----------------------------------------------------------------------

@@ -28,6 +28,8 @@ CASES = {
     # config 1 (BASELINE.json configs[0]): Rosenbrock n=1e4, m=5, backtracking, x0~U(-2,2) seed 42
     "rosen_n1e4_m5_bt": ("rosenbrock", 10000, 5, "backtracking", 1000, 1e-5, 42, -2.0, 2.0, 3),
     "rosen_n100_m5_bt": ("rosenbrock", 100, 5, "backtracking", 200, 1e-5, 42, -2.0, 2.0, 51),
+    # m = 16, the batched solver's largest history: the ring wraps 11 times in 200 iterations
+    "rosen_n100_m16_bt": ("rosenbrock", 100, 16, "backtracking", 200, 1e-5, 42, -2.0, 2.0, 51),
     "rosen_n1e3_m10_bt_conv": ("rosenbrock", 1000, 10, "backtracking", 20000, 1e-5, 42, -2.0, 2.0, 1),
     "rosen_n1e4_m5_interp": ("rosenbrock", 10000, 5, "interpolation", 300, 1e-5, 42, -2.0, 2.0, 1),
     "rosen_n1e4_m5_wolfe": ("rosenbrock", 10000, 5, "wolfe", 300, 1e-5, 42, -2.0, 2.0, 1),

@@ -1,4 +1,5 @@
-"""Conditions on the inputs of tests/test_gpu_constants.py, asserted on the oracle alone (CPU).
+"""Conditions on the inputs of tests/test_gpu_constants.py and of the varied-constants cases of
+tests/devobj_gpu_cases.py and tests/batchcb_gpu_cases.py, asserted on the oracle alone (CPU).
 
 A parity test with varied constants passes vacuously where the constants never bite. For the exact
 cases the GPU tests run (tests/consts_cases.py), this file asserts everything they rely on: every
@@ -144,6 +145,70 @@ def test_batch_dense_cases(case):
     for q in K.BATCH_DENSE_Q:
         o, d = K.oracle(case, seed=10 + q, dense_q=q), K.oracle(case, seed=10 + q, dense_q=q, default=True)
         assert finite(o) and differs(o, d), q
+
+
+@pytest.mark.parametrize("case", K.DEVICE_OBJ, ids=_id)
+def test_device_objective_cases(case):
+    """path 11: the objective as callables, as the device callback evaluates it"""
+    o, d = K.oracle(case, host=True), K.oracle(case, host=True, default=True)
+    assert finite(o) and differs(o, d)
+    assert accepted(case, o)[1] > 0
+
+
+@pytest.mark.parametrize("case", K.BATCH_CALLBACK, ids=_id)
+def test_batch_callback_cases(case):
+    """path 12. Three of the four starts or more leave the default constants' run (the start at the
+    minimiser takes the default steps under K1 / K5 + Wolfe at n = 513, the scaled one under K1 +
+    interpolation at n = 5), and each entry reaches what its comment in consts_cases.py says."""
+    ks, obj, n, m, ls, iters = case
+    k = K.SETS[ks]
+    runs = [K.oracle(case, host=True, x0=x0) for x0 in K.batch_x0(n)]
+    dflt = [K.oracle(case, host=True, x0=x0, default=True) for x0 in K.batch_x0(n)]
+    assert all(finite(o) for o in runs)
+    assert sum(differs(o, d) for o, d in zip(runs, dflt)) >= 3
+    failed = [o["status"] == "ls_failed" for o in runs]
+    if ks in ("K1", "K5") and ls == "wolfe":  # a mixed batch: three fail at iteration 1, one runs on
+        assert [o["iters"] for o in runs if o["status"] == "ls_failed"] == [1, 1, 1] and sum(failed) == 3
+        assert [o["iters"] for o in runs if o["status"] != "ls_failed"] == [iters]
+    elif ks == "K2" and ls == "wolfe":  # expands above initial_step in every iteration of every problem
+        assert all(np.all(steps(o) > k["initial_step"]) and o["iters"] == iters for o in runs)
+        assert all(o["nf_total"] >= 20 * iters for o in runs)
+    elif ks == "K3" and ls == "backtracking_wolfe":  # the step grows by 1.1 some 24 times per search, two f values a trial
+        assert all(o["iters"] == iters and o["nf_total"] >= 40 * iters for o in runs)
+        assert all(np.sum(steps(o) > 5 * k["initial_step"]) >= iters - 1 for o in runs)
+    elif ks == "K3" and ls == "wolfe":  # problems that end inside their first search, beside one that runs on
+        assert sorted(o["iters"] for o in runs) == [0, 0, 0, iters] and sum(failed) == 3
+    elif ks == "K4":  # fails at once
+        assert all(failed) and all(o["iters"] == 0 for o in runs)
+    else:
+        assert not any(failed) and all(accepted(case, o)[1] > 0 for o in runs)
+    if ks == "K2" and ls != "wolfe":
+        assert all(accepted(case, o)[0] == 0 for o in runs)  # no first step accepted
+
+
+def test_long_search_case():
+    """backtracking_alpha = 0.99: the middle row's first search rejects 300 steps or more, the rows
+    beside it converge at their first evaluation"""
+    c = K.LONG_SEARCH
+    runs = [O.lbfgs(c["objective"], x0, c["search"], c["m"], c["iterations"], K.TOL, mode=O.CANON, consts=c["consts"])
+            for x0 in K.long_search_x0()]
+    for p, o in enumerate(runs):
+        if p == c["row"]:
+            j = chain_length(o["alpha"][0], 1.0, c["consts"]["backtracking_alpha"], limit=2000)
+            assert j is not None and j >= c["rejected_at_least"], (o["alpha"], j)
+            assert o["iters"] == c["iterations"] and finite(o)
+        else:
+            assert o["iters"] == 0 and o["status"] == "converged"
+
+
+@pytest.mark.parametrize("case", K.BATCH_RAGGED + K.BATCH_RAGGED_DENSE, ids=K.ragged_id)
+def test_batch_ragged_cases(case):
+    """path 13: every problem of every batch, at its own size"""
+    subs = K.ragged_problems(case)
+    assert len({s[0][2] for s in subs}) >= 2  # sizes differ within the batch
+    for sub, kw in subs:
+        o, d = K.oracle(sub, **kw), K.oracle(sub, default=True, **kw)
+        assert finite(o) and differs(o, d), (sub, kw)
 
 
 @pytest.mark.parametrize("ks,ls", K.LINE_SEARCH)

@@ -7,7 +7,8 @@ Shapes are the smallest at which each mechanism can go wrong: n = 5 (one partial
 edges in one wave), 512 (exactly one full segment), 513 (a second segment of one element: the seam
 halo meets a 1-element segment), 1537 (four segments, the last of one element), 32768 (64
 segments: every lane of the stage-2 wave live); m = 1 (a two-loop with no q pass), m = 5 with 12
-iterations (the ring and the spare pair rotate)."""
+iterations (the ring and the spare pair rotate), m = 16 and 8 with 40 iterations at most (the largest
+history the batch accepts, filled and rotated; tests/hist_cases.py)."""
 import ctypes
 import os
 import sys
@@ -17,6 +18,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cuda-lbfgs_amd"))
+import hist_cases as HC  # noqa: E402
 import lbfgs_amd as L  # noqa: E402
 import oracle_lib as O  # noqa: E402
 
@@ -278,3 +280,22 @@ def test_refusals():
         for problem in (-1, B):
             assert lib.lbfgs_batch_trace_len(b.h, problem) == -1
             assert lib.lbfgs_batch_events_get(b.h, problem, ctypes.byref(ev)) == -1
+
+
+# ---- 9. a history of 16 pairs, and of 8 -----------------------------------------------------------
+@pytest.mark.parametrize("case", HC.STENCIL, ids=HC.case_id)
+def test_long_history(case):
+    """m = 16 (LBK_SMALL_HMAX: ring[16], sy[17], yy[17], TA[16], the spare pair in pool slot 16) and
+    m = 8, on inputs that fill the ring and rotate it (tests/test_history_inputs.py asserts that on the
+    CPU): the oracle's bits, and everything the single-problem path reports."""
+    obj, n, m, ls, tol, differ = case
+    X0, orc = HC.stencil_x0(case), HC.stencil_oracle(case)
+    with L.Batch(n, m, len(X0)) as b:
+        res = b.minimize(obj, X0, ls, max_iterations=HC.MAXIT, tolerance=tol, trace=True)
+    with L.Context(n, m) as c:
+        for p in range(len(X0)):
+            check_problem(res, p, orc[p], case)
+            assert [res["events"][p][k] for k in EVENT_KEYS] == message_counts(orc[p])[:4], (case, p)
+            HC.check_single(res, p, c.minimize(obj, X0[p], ls, max_iterations=HC.MAXIT, tolerance=tol, trace=True), case)
+    HC.check_h_max(res, orc, m, case)
+    assert not differ or len(set(res["iterations"])) >= 2

@@ -8,7 +8,10 @@ tests/batchcb_gpu_cases.py:
 4. launch shape;
 5. real device math: torch objectives per row, host and device forms, a non-default torch stream;
 6. the guard paths: not-descent fallback, skipped updates, a failed line search;
-7. refusals, a callback returning nonzero, a Python exception, clearing, the other objectives.
+7. refusals, a callback returning nonzero, a Python exception, clearing, the other objectives;
+8. a history of 16 pairs and of 8, filled and rotated;
+9. the size limit, n = 32768;
+10. line-search constants that are not the defaults, and one row alone in a search of hundreds of rounds.
 
 They run once, together, in a child pytest that imports torch first (tests/test_gpu_device_objective.py
 says why); every test below reports one function of that run.
@@ -41,6 +44,10 @@ FUNCTIONS = {
     "test_callback_returning_nonzero_then_the_batch_goes_on": 1,
     "test_python_exception_is_reraised": 1,
     "test_other_objectives_of_the_batch_are_undisturbed": 1,
+    "test_long_history": 20,
+    "test_size_limit": 1,
+    "test_varied_constants": 52,
+    "test_one_row_alone_in_a_long_search": 1,
 }
 
 

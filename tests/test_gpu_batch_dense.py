@@ -8,7 +8,9 @@ search, the single-problem path (Context.set_dense_quadratic + Context.minimize)
 Shapes: n = 2 and 3 (fewer rows than waves), 5 (a row beyond a multiple of 4), 10, 100 (a second,
 partial lane stride), 64 / 65 (exactly one lane stride; one element more), 513 (two canonical
 segments, the second of one element), 500 (the largest known-answer fixture); m = 1 (a two-loop with
-no q pass) and m = 5 with more than m + 2 iterations (the ring and the spare pair rotate)."""
+no q pass) and m = 5 with more than m + 2 iterations (the ring and the spare pair rotate); m = 16, the
+largest history a batch accepts, with 40 iterations at most at n = 65 and 513 (tests/hist_cases.py);
+n = 4096, the largest size, and 4095 (the last lane stride and the last group of four rows partial)."""
 import os
 import sys
 
@@ -17,6 +19,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cuda-lbfgs_amd"))
+import hist_cases as HC  # noqa: E402
 import lbfgs_amd as L  # noqa: E402
 import oracle_lib as O  # noqa: E402
 
@@ -257,6 +260,62 @@ def test_data_replaced_between_solves():
             assert same_bits(np.asarray(second[k][p], np.float64), np.asarray(fresh[k][p], np.float64)), (k, p)
         assert stencil["status"][p] == o3["status"] and stencil["iterations"][p] == o3["iters"]
         assert same_bits(stencil["x"][p], o3["x"]) and same_bits(stencil["tr_f"][p], o3["f"])
+
+
+# ---- 8b. a history of 16 pairs --------------------------------------------------------------------
+@pytest.mark.parametrize("case", HC.DENSE, ids=HC.case_id)
+def test_long_history(case):
+    """m = 16 (the largest history a batch accepts), 40 iterations at most, three problems of which one
+    ends earlier; tests/test_history_inputs.py asserts on the CPU that the ring fills and rotates. The
+    oracle's bits, and everything the single-problem path reports."""
+    n, m, ls = case
+    A, b, X0 = HC.dense_data(n)
+    orc = HC.dense_oracle(case)
+    res = solve(n, m, A, b, X0, ls, HC.MAXIT, HC.DENSE_TOL)
+    with L.Context(n, m) as c:
+        for p in range(len(X0)):
+            check_problem(res, p, orc[p], case)
+            c.set_dense_quadratic(A[p], b[p])
+            one = c.minimize("dense", X0[p], ls, max_iterations=HC.MAXIT, tolerance=HC.DENSE_TOL, trace=True)
+            HC.check_single(res, p, one, case)
+    HC.check_h_max(res, orc, m, case)
+    assert len(set(res["iterations"])) >= 2
+
+
+# ---- 8c. the size limit ---------------------------------------------------------------------------
+def dominant_batch(n, B, seed):
+    """A_p symmetric with a diagonal of 1 ... 100 (logarithmically spaced) and off-diagonal entries in
+    [-0.5 / n, 0.5 / n]: every Gershgorin disc lies right of 0.5, so A_p is positive definite, and no
+    factorisation is needed to make it."""
+    A, b, X0 = [], [], []
+    for p in range(B):
+        rs = np.random.RandomState(seed + p)
+        R = rs.uniform(-0.5 / n, 0.5 / n, (n, n))
+        M = (R + R.T) / 2
+        M[np.diag_indices(n)] = np.logspace(0, 2, n)
+        A.append(M)
+        b.append(rs.uniform(-1.0, 1.0, n))
+        X0.append(O.x0_uniform(n, seed + p, -2.0, 2.0))
+    return np.stack(A), np.stack(b), np.stack(X0)
+
+
+@pytest.mark.parametrize("n", [L.DENSE_BATCH_NMAX, L.DENSE_BATCH_NMAX - 1])
+def test_size_limit(n):
+    """n = 4096, the largest the dense batch accepts (64 full lane strides per row, 1024 full groups of
+    four rows), and 4095 (the last lane stride and the last group of rows partial): B = 2, m = 3, 5
+    iterations, against the oracle and the single-problem path."""
+    m, B, ls, maxit = 3, 2, "backtracking", 5
+    A, b, X0 = dominant_batch(n, B, 7000 + n)
+    orc = oracle(("limit", n), A, b, X0, ls, m, maxit, 1e-5)
+    assert all(orc[p]["iters"] == maxit and message_counts(orc[p]) == [0] * 5 for p in range(B))  # (CPU) h reaches m
+    res = solve(n, m, A, b, X0, ls, maxit)
+    with L.Context(n, m) as c:
+        for p in range(B):
+            check_problem(res, p, orc[p], ("limit", n))
+            c.set_dense_quadratic(A[p], b[p])
+            HC.check_single(res, p, c.minimize("dense", X0[p], ls, max_iterations=maxit, tolerance=1e-5, trace=True),
+                            ("limit", n))
+    assert list(res["h_max"]) == [m] * B
 
 
 # ---- 9. refusals ---------------------------------------------------------------------------------

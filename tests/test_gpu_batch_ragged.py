@@ -7,7 +7,9 @@ problem's own n_p (for dense after O.dense_set(A_p, b_p)).
 Sizes are the smallest at which each mechanism can go wrong: 513 (a second segment of one element),
 5 (one partial row), 1537 (four segments, the last of one element), 512 (exactly one segment), 129
 (one row of a wave plus one element), 1024 (two full segments), 32768 beside 5 (64 segments beside
-one: every lane of the stage-2 wave live for one problem and one lane for the next)."""
+one: every lane of the stage-2 wave live for one problem and one lane for the next); m = 16 and 8 with
+sizes [1537, 17, 513] (stencil) and [513, 65, 100] (dense), 40 iterations at most: the largest history a
+batch accepts, filled and rotated beside problems of other sizes (tests/hist_cases.py)."""
 import ctypes as C
 import os
 import sys
@@ -17,6 +19,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cuda-lbfgs_amd"))
+import hist_cases as HC  # noqa: E402
 import lbfgs_amd as L  # noqa: E402
 import oracle_lib as O  # noqa: E402
 
@@ -340,6 +343,45 @@ def test_dense_counters_replaced_data_and_a_stencil_solve_after():
         assert same_bits(first["x"][p], one["x"]) and same_bits(first["tr_f"][p], one["tr_f"]), p
         for k in ("trials_f", "trials_fg", "commits", "h_min", "h_max", "iterations"):
             assert first[k][p] == one[k], (p, k, first[k][p], one[k])
+
+
+# ---- 8b. a history of 16 pairs, and of 8, beside problems of other sizes -------------------------------------
+def _single(n, m, obj, x0, ls, tol, dense=None):
+    with L.Context(n, m) as c:
+        if dense is not None:
+            c.set_dense_quadratic(*dense)
+        return c.minimize(obj, x0, ls, max_iterations=HC.MAXIT, tolerance=tol, trace=True)
+
+
+@pytest.mark.parametrize("case", HC.RAGGED_STENCIL, ids=HC.case_id)
+def test_long_history(case):
+    """m = 16 (the largest history a batch accepts) and m = 8 with sizes [1537, 17, 513] in one batch, on
+    inputs that fill the ring and rotate it (tests/test_history_inputs.py asserts that on the CPU): the
+    oracle's bits, and everything one single-problem solve per problem reports."""
+    obj, sizes, starts, m, ls, tol, differ = case
+    X0, orc = HC.ragged_x0(case), HC.stencil_oracle(case)
+    res = solve(sizes, m, obj, X0, ls, HC.MAXIT, tol)
+    for p, n in enumerate(sizes):
+        check_problem(res, p, orc[p], case)
+        HC.check_single(res, p, _single(n, m, obj, X0[p], ls, tol), case)
+    HC.check_h_max(res, orc, m, case)
+    assert len(set(res["iterations"])) >= 2
+
+
+@pytest.mark.parametrize("case", HC.RAGGED_DENSE, ids=HC.case_id)
+def test_dense_long_history(case):
+    """the same in the dense kernels: sizes [513, 65, 100], m = 16, 40 iterations at most"""
+    sizes, m, ls = case
+    A, b, X0 = HC.ragged_dense_data()
+    orc = HC.dense_oracle(case)
+    with L.Batch(list(sizes), m) as bt:
+        bt.set_dense_quadratics(A, b)
+        res = bt.minimize("dense", X0, ls, max_iterations=HC.MAXIT, tolerance=HC.DENSE_TOL, trace=True)
+    for p, n in enumerate(sizes):
+        check_problem(res, p, orc[p], case)
+        HC.check_single(res, p, _single(n, m, "dense", X0[p], ls, HC.DENSE_TOL, dense=(A[p], b[p])), case)
+    HC.check_h_max(res, orc, m, case)
+    assert len(set(res["iterations"])) >= 2
 
 
 # ---- 9. refusals ------------------------------------------------------------------------------------------

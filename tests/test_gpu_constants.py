@@ -6,7 +6,9 @@ on the CPU that the constants bite in each case; tests/test_oracle_consts.py pin
 these constants to the reference's own code. Here every path is compared, bit for bit, with the
 canonical-order oracle run with the same constants (the f / |g| / step traces, the x checksums, the
 final x, status, iteration count and messages) and, where it has an off-switch, with the
-switched-off run (the same bits and counters). Each case asserts that its path ran.
+switched-off run (the same bits and counters). Each case asserts that its path ran. Paths 11 (the
+device-callback objective) and 12 (the batched callback) need torch in the process and are in
+tests/devobj_gpu_cases.py and tests/batchcb_gpu_cases.py; path 13, ragged batches, is here.
 """
 import os
 import sys
@@ -246,6 +248,31 @@ def test_batch_dense(case):
             for p in range(len(X0)):
                 c.set_dense_quadratic(A[p], bb[p])
                 check_single(res, p, c.minimize("dense", X0[p], ls, iters, tolerance=K.TOL, consts=k), case)
+
+
+# ---- 13. ragged batches ---------------------------------------------------------------------------
+@pytest.mark.parametrize("case", K.BATCH_RAGGED + K.BATCH_RAGGED_DENSE, ids=K.ragged_id)
+def test_batch_ragged(case):
+    """the same constants in the ragged stencil and dense kernels: problems of different sizes in one
+    batch, each against the oracle and against a single-problem solve of its own, counters included"""
+    ks, obj, sizes, m, ls, iters = case
+    subs = K.ragged_problems(case)
+    orc = [K.oracle(sub, **kw) for sub, kw in subs]
+    X0 = [o["x0"] for o in orc]
+    k = K.device_constants(L, ks)
+    data = [K.dense_problem(sub[2], kw["dense_q"]) for sub, kw in subs] if obj == "dense" else None
+    with L.Batch(list(sizes), m) as b:
+        assert b.ragged
+        if data:
+            b.set_dense_quadratics([d[0] for d in data], [d[1] for d in data])
+        res = b.minimize(obj, X0, ls, max_iterations=iters, tolerance=K.TOL, consts=k, trace=True)
+    assert res["launches"] > 0
+    for p, o in enumerate(orc):
+        check_problem(res, p, o, case)
+        with L.Context(sizes[p], m) as c:
+            if data:
+                c.set_dense_quadratic(*data[p])
+            check_single(res, p, c.minimize(obj, X0[p], ls, iters, tolerance=K.TOL, consts=k), case)
 
 
 # ---- 8. lbfgs_line_search alone -------------------------------------------------------------------

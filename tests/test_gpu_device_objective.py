@@ -2,7 +2,8 @@
 caller-owned buffers (lbfgs_reducer_*) and their torch front end, on the GPU. Everything compares
 bits. The cases themselves are in tests/devobj_gpu_cases.py:
 
-1. the device callback against the oracle and the host-callback path, call counts included;
+1. the device callback against the oracle and the host-callback path, call counts included, also with
+   line-search constants that are not the defaults;
 2. real device math: torch objectives reduced through Reducer.sum, through LBFGS_OBJ_DEVICE and
    through LBFGS_OBJ_HOST, also on a non-default torch stream;
 3. minimize_device / init_device / get_x_device against the host-buffer forms;
@@ -31,6 +32,7 @@ CASES = os.path.join(ROOT, "tests", "devobj_gpu_cases.py")
 # test function of the child run -> its number of cases
 FUNCTIONS = {
     "test_device_callback_vs_oracle_and_host_path": 9,
+    "test_device_callback_with_varied_constants": 24,
     "test_torch_objective_device_vs_host_route": 4,
     "test_torch_objective_on_a_side_stream": 1,
     "test_minimize_device_equals_minimize": 15,

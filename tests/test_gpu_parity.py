@@ -167,7 +167,8 @@ def test_trajectory_bit_exact_vs_canonical_oracle(name):
 # bit-exact with the canonical oracle, so these are its horizons. No parallel reduction order
 # can extend them much: they are set by the reference's own left-to-right rounding.
 HORIZON = {"qsep_main": (2, 2), "qtri_n1e4_m10_bt": (10, 10), "qtri_n1e4_m20_wolfe": (2, 3),
-           "qtri_n1e5_m20_wolfe": (2, 3), "rosen_n100_m5_bt": (47, 39), "rosen_n1_bt": (1, 1),
+           "qtri_n1e5_m20_wolfe": (2, 3), "rosen_n100_m5_bt": (47, 39), "rosen_n100_m16_bt": (49, 30),
+           "rosen_n1_bt": (1, 1),
            "rosen_n1e3_m10_bt_conv": (49, 35), "rosen_n1e4_m5_bt": (67, 45),
            "rosen_n1e4_m5_btw": (68, 45), "rosen_n1e4_m5_interp": (67, 45),
            "rosen_n1e4_m5_wolfe": (28, 15), "rosen_n1e5_m10_bt": (61, 26),
