@@ -20,6 +20,18 @@
  * materialised (k_last), the remaining trials run as k_trial passes and the commit is redone
  * at the accepted step. Results are bit-identical to running the reference's steps
  * separately in the canonical reduction order (oracle/lbfgs_oracle.c, ORC_CANON).
+ *
+ * The three iteration loops - iterate (the schedule above and its small-n, persistent and unfused
+ * forms), iterate_vf (vector-free) and iterate_cuda (the CUDA path) - and the entry points beside
+ * them state each step they share once:
+ *   iterate_top                trace entry, verbose line, convergence test
+ *   ring_view / ring_push      the history ring read in ring order / advanced by one pair (the
+ *                              speculative launch predicts with the same push); swap_iterates
+ *   twoloop_passes             the launch sequence above, also lbfgs_dev_twoloop's
+ *   last_update                the record of the update the commit, a trial pass or k_last forms
+ *   vf_combine                 the vector-free coefficient sums, in the oracle's order
+ *   cache_f / cache_g          what an external objective has evaluated at the trial point
+ *   cu_interpolation, cu_wolfe the CUDA path's searches, L-BFGS.cu's and the variant files'
  */
 #define _POSIX_C_SOURCE 199309L
 #include <float.h>
@@ -667,6 +679,24 @@ static int host_point(lbfgs_ctx* c, double alpha) {
     return 0;
 }
 
+/* f(z(alpha)) is now known */
+static void cache_f(lbfgs_ctx* c, double alpha, double f) {
+    c->hf_valid = 1;
+    c->hf_alpha = alpha;
+    c->hf_val = f;
+}
+
+/* grad(z(alpha)) is now in dst: cached if dst is gt, else a gt cached at this alpha is dropped
+ * (the values of the latest call are the ones used) */
+static void cache_g(lbfgs_ctx* c, double alpha, const double* dst) {
+    if (dst == c->gt) {
+        c->gt_valid = 1;
+        c->gt_alpha = alpha;
+    } else if (c->gt_valid && c->gt_alpha == alpha) {
+        c->gt_valid = 0;
+    }
+}
+
 /* f(z(alpha)); fresh = 1 calls f even if it was evaluated at this point before */
 static int host_f_at(lbfgs_ctx* c, double alpha, int fresh, double* f) {
     if (!fresh && c->hf_valid && c->hf_alpha == alpha && c->hz_valid && c->hz_alpha == alpha) {
@@ -678,24 +708,18 @@ static int host_f_at(lbfgs_ctx* c, double alpha, int fresh, double* f) {
     if (c->obj == LBFGS_OBJ_DENSE_QUAD) { /* f and, for free, grad into gt */
         DEV(lbk_dense_eval(c->dev, c->xn, c->gt, SLOT_TRIAL(c->m)));
         DEVNC(lbk_fetch(c->dev, SLOT_TRIAL(c->m), 1, f));
-        c->gt_valid = 1;
-        c->gt_alpha = alpha;
+        cache_g(c, alpha, c->gt);
     } else if (c->obj == LBFGS_OBJ_DEVICE) {
         /* LBFGS_DEVICE_EAGER_GRAD: the gradient with every f, into gt as the dense objective's */
         const int eager = (c->dcb.flags & LBFGS_DEVICE_EAGER_GRAD) != 0;
         rc = device_eval(c, c->xn, f, eager ? c->gt : NULL);
         if (rc) return rc;
-        if (eager) {
-            c->gt_valid = 1;
-            c->gt_alpha = alpha;
-        }
+        if (eager) cache_g(c, alpha, c->gt);
     } else {
         *f = c->cb.f(c->hx, c->n, c->cb.user);
         c->cb_f++;
     }
-    c->hf_valid = 1;
-    c->hf_alpha = alpha;
-    c->hf_val = *f;
+    cache_f(c, alpha, *f);
     return 0;
 }
 
@@ -711,47 +735,22 @@ static int host_g_at(lbfgs_ctx* c, double alpha, int fresh, double* dst) {
         double f;
         DEV(lbk_dense_eval(c->dev, c->xn, dst, SLOT_TRIAL(c->m)));
         DEVNC(lbk_fetch(c->dev, SLOT_TRIAL(c->m), 1, &f));
-        c->hf_valid = 1;
-        c->hf_alpha = alpha;
-        c->hf_val = f;
-        if (dst == c->gt) {
-            c->gt_valid = 1;
-            c->gt_alpha = alpha;
-        } else if (c->gt_valid && c->gt_alpha == alpha) {
-            c->gt_valid = 0;
-        }
-        return 0;
-    }
-    if (c->obj == LBFGS_OBJ_DEVICE) { /* f with it where this point's is not cached yet */
+        cache_f(c, alpha, f);
+    } else if (c->obj == LBFGS_OBJ_DEVICE) { /* f with it where this point's is not cached yet */
         const int need_f = !(c->hf_valid && c->hf_alpha == alpha);
         double f = 0.0;
         rc = device_eval(c, c->xn, need_f ? &f : NULL, dst);
         if (rc) return rc;
-        if (need_f) {
-            c->hf_valid = 1;
-            c->hf_alpha = alpha;
-            c->hf_val = f;
-        }
-        if (dst == c->gt) {
-            c->gt_valid = 1;
-            c->gt_alpha = alpha;
-        } else if (c->gt_valid && c->gt_alpha == alpha) {
-            c->gt_valid = 0;
-        }
-        return 0;
+        if (need_f) cache_f(c, alpha, f);
+    } else {
+        const int b = c->hg_cur;
+        c->hg_cur ^= 1;
+        DEVNC(lbk_xfer_wait(c->dev, XF_G0 + b)); /* the upload that last read this buffer */
+        c->cb.grad(c->hx, c->n, c->hg[b], c->cb.user);
+        c->cb_g++;
+        DEVNC(lbk_upload_local_async(c->dev, dst, c->hg[b], XF_G0 + b));
     }
-    const int b = c->hg_cur;
-    c->hg_cur ^= 1;
-    DEVNC(lbk_xfer_wait(c->dev, XF_G0 + b)); /* the upload that last read this buffer */
-    c->cb.grad(c->hx, c->n, c->hg[b], c->cb.user);
-    c->cb_g++;
-    DEVNC(lbk_upload_local_async(c->dev, dst, c->hg[b], XF_G0 + b));
-    if (dst == c->gt) {
-        c->gt_valid = 1;
-        c->gt_alpha = alpha;
-    } else if (c->gt_valid && c->gt_alpha == alpha) {
-        c->gt_valid = 0;
-    }
+    cache_g(c, alpha, dst);
     return 0;
 }
 
@@ -1121,9 +1120,67 @@ static int commit(lbfgs_ctx* c, int dmode, double alpha, int cslot, double* tot,
 /* ------------------------------------------------------------------------------------------
  * One iteration of lbfgs.cpp:72-199. Returns 0 to continue, 1 when finished, < 0 on error.
  * ---------------------------------------------------------------------------------------- */
-static void note_h(lbfgs_ctx* c) {
-    if (c->h_min < 0 || c->h < c->h_min) c->h_min = c->h;
-    if (c->h > c->h_max) c->h_max = c->h;
+static void note_h(lbfgs_ctx* c, int h) {
+    if (c->h_min < 0 || h < c->h_min) c->h_min = h;
+    if (h > c->h_max) c->h_max = h;
+}
+
+/* the top of an iteration (:72-84): the trace entry, the verbose line, the convergence test.
+ * Returns 1 when converged. */
+static int iterate_top(lbfgs_ctx* c) {
+    const double gnorm = sqrt(c->gg);
+    const int rc = trace_push(c, c->f_cur, gnorm, 1);
+    if (rc) return rc;
+    if (c->flags & LBFGS_FLAG_VERBOSE) { /* :76-78 */
+        printf("Iteration %d, f = %g, |grad| = %g\n", c->k, c->f_cur, gnorm);
+        fflush(stdout);
+    }
+    if (gnorm < c->tol) { /* :80-84 */
+        say(c, "Converged!\n");
+        c->status = LBFGS_STATUS_CONVERGED;
+        return 1;
+    }
+    note_h(c, c->h);
+    return 0;
+}
+
+/* The history ring, shared by every path that reads or advances it.
+ * ring_view: the h pairs of a ring in ring order (oldest first) - rho_i = 1 / s_i.y_i and / or
+ * the pairs' vectors, whichever is asked for. */
+static void ring_view(const lbfgs_ctx* c, const int* ring, int h, double* rho, const double** Sr,
+                      const double** Yr) {
+    for (int i = 0; i < h; ++i) {
+        if (rho) rho[i] = 1.0 / c->sy[ring[i]];
+        if (Sr) {
+            Sr[i] = c->S[ring[i]];
+            Yr[i] = c->Y[ring[i]];
+        }
+    }
+}
+
+/* ring_push (:182-191): the pair in pool slot *free_pair becomes the newest. A full ring drops its
+ * oldest pair, whose slot is the next free one; otherwise pool slots 0..h-1 are used and h is free. */
+static void ring_push(int m, int* ring, int* h, int* free_pair) {
+    const int pair = *free_pair;
+    if (*h >= m) {
+        const int oldest = ring[0];
+        for (int i = 0; i + 1 < m; ++i) ring[i] = ring[i + 1];
+        ring[m - 1] = pair;
+        *free_pair = oldest;
+    } else {
+        ring[(*h)++] = pair;
+        *free_pair = *h;
+    }
+}
+
+/* x = x_new, g = g_new (:197-198): the buffers trade places */
+static void swap_iterates(lbfgs_ctx* c) {
+    double* t = c->x;
+    c->x = c->xn;
+    c->xn = t;
+    t = c->g;
+    c->g = c->gn;
+    c->gn = t;
 }
 
 /* the backtracking search's second step, f reduced by the commit pass (line_search.cpp:26) */
@@ -1159,26 +1216,15 @@ static int spec_drop(lbfgs_ctx* c) {
 static int spec_next(lbfgs_ctx* c, double decided) {
     const int m = c->m, h = c->h, k = c->k;
     if (!c->spec_on || c->steps_left <= 0 || c->cur_epoch == 0 || c->K.initial_step < 1e-10) return 0;
-    const int h1 = h < m ? h + 1 : m;
+    int ring1[MMAX + 1], h1 = h, free1 = c->free_pair; /* the ring after the push */
+    memcpy(ring1, c->ring, sizeof(int) * (size_t)h);
+    ring_push(m, ring1, &h1, &free1);
     if (!lbk_small_spec_ok(c->dev, h1)) return 0;
-    int ring1[MMAX + 1], free1;
-    if (h >= m) {
-        for (int i = 0; i + 1 < m; ++i) ring1[i] = c->ring[i + 1];
-        ring1[m - 1] = c->free_pair;
-        free1 = c->ring[0];
-    } else {
-        for (int i = 0; i < h; ++i) ring1[i] = c->ring[i];
-        ring1[h] = c->free_pair;
-        free1 = h + 1;
-    }
     const double* Sr[MMAX];
     const double* Yr[MMAX];
     double rho1[MMAX];
-    for (int i = 0; i < h1; ++i) {
-        Sr[i] = c->S[ring1[i]];
-        Yr[i] = c->Y[ring1[i]];
-        rho1[i] = i + 1 < h1 ? 1.0 / c->sy[ring1[i]] : 0.0; /* the new pair's: the kernel's */
-    }
+    ring_view(c, ring1, h1, rho1, Sr, Yr);
+    rho1[h1 - 1] = 0.0; /* the new pair's: the kernel's */
     const int cslot = SLOT_COMMIT0 + (k & 1), cslot1 = SLOT_COMMIT0 + ((k + 1) & 1);
     const int p01 = REF(cslot, LBK_C_SG);
     lbk_spec sp;
@@ -1236,11 +1282,7 @@ static int small_fetch(lbfgs_ctx* c, int cslot, double* tot) {
         double rho[MMAX];
         const double* Sr[MMAX];
         const double* Yr[MMAX];
-        for (int i = 0; i < c->h; ++i) {
-            rho[i] = 1.0 / c->sy[c->ring[i]];
-            Sr[i] = c->S[c->ring[i]];
-            Yr[i] = c->Y[c->ring[i]];
-        }
+        ring_view(c, c->ring, c->h, rho, Sr, Yr);
         int rc = small_launch(c, rho, Sr, Yr, c->cur_gamma, c->cur_p0);
         if (rc) return rc;
         DEVNC(lbk_small_fetch(c->dev, c->cur_epoch, cslot, 8, tot, NULL, NULL, NULL));
@@ -1286,22 +1328,58 @@ static int spec_matches(const lbfgs_ctx* c, int h, const double* rho, int p0_ref
     return 1;
 }
 
+/* The two-loop passes as separate launches, over h pairs in ring order: s_{h-1}.g unless sg_ref
+ * (>= 0) names it among the previous commit's reductions, the first loop down to k_mid, the second
+ * loop up to its last update, which is left to the commit (or k_last; last_update).
+ * q and r are updated in place as far as the driver is concerned. The device layer keeps the two
+ * ends of each vector in place - the tail the alternating walk re-reads from the Infinity Cache -
+ * and ping-pongs the segments between them through an alternate buffer of its own
+ * (LBFGS_WORK_SPLIT, DESIGN.md §4 "Split work vector"). A ping-pong of the whole vectors measured
+ * neutral at 1e8 and -8 % at 1e7: it gives up the cached ends. */
+static int twoloop_passes(lbfgs_ctx* c, int h, const double* rho, const double* const* Sr,
+                          const double* const* Yr, double gamma, int sg_ref) {
+    const int m = c->m;
+    int refA[MMAX], refB[MMAX];
+    if (sg_ref >= 0) {
+        refA[h - 1] = sg_ref; /* s_{h-1}.g from the previous commit */
+    } else {
+        DEV(lbk_dot(c->dev, Sr[h - 1], c->g, SLOT_P0));
+        refA[h - 1] = REF(SLOT_P0, 0);
+    }
+    const double* qsrc = c->g;
+    for (int i = h - 2; i >= 0; --i) {
+        DEV(lbk_axpy_dot(c->dev, c->q, qsrc, Yr[i + 1], Sr[i], rho[i + 1], refA[i + 1], SLOT_A0 + i));
+        refA[i] = REF(SLOT_A0 + i, 0);
+        qsrc = c->q;
+    }
+    DEV(lbk_mid(c->dev, c->r, qsrc, Yr[0], rho[0], gamma, refA[0], SLOT_B0(m)));
+    refB[0] = REF(SLOT_B0(m), 0);
+    for (int i = 0; i + 1 < h; ++i) {
+        DEV(lbk_axpy2_dot(c->dev, c->r, c->r, Sr[i], Yr[i + 1], rho[i], refB[i], refA[i], SLOT_B0(m) + i + 1));
+        refB[i + 1] = REF(SLOT_B0(m) + i + 1, 0);
+    }
+    return 0;
+}
+
+/* the record of the second loop's last update, d = -(r + s_{h-1} (alpha_{h-1} - beta_{h-1})), which
+ * the commit, a trial pass or k_last forms: the same slots whichever form ran the passes before it
+ * (alpha_{h-1} = s_{h-1}.g: sg_ref, or SLOT_P0 where the passes reduced it themselves) */
+static void last_update(lbfgs_ctx* c, int h, double rho, int sg_ref) {
+    c->rc = c->r;
+    c->rho_last = rho;
+    c->ref_b_last = REF(SLOT_B0(c->m) + h - 1, 0);
+    c->ref_a_last = sg_ref >= 0 ? sg_ref : REF(SLOT_P0, 0);
+    c->s_last_pair = c->ring[h - 1];
+}
+
 static int iterate(lbfgs_ctx* c) {
     const int k = c->k, m = c->m, h = c->h;
-    const double gnorm = sqrt(c->gg);
-    int rc = trace_push(c, c->f_cur, gnorm, 1);
-    if (rc) return rc;
-    if (c->flags & LBFGS_FLAG_VERBOSE) { /* :76-78 */
-        printf("Iteration %d, f = %g, |grad| = %g\n", k, c->f_cur, gnorm);
-        fflush(stdout);
-    }
-    if (gnorm < c->tol) { /* :80-84 */
-        say(c, "Converged!\n");
-        c->status = LBFGS_STATUS_CONVERGED;
+    int rc = iterate_top(c);
+    if (rc == 1) {
         rc = spec_drop(c);
         return rc ? rc : 1;
     }
-    note_h(c);
+    if (rc) return rc;
 
     /* ---- search direction (:87-143) ---- */
     int dmode = LBK_D_NEG_G;
@@ -1334,101 +1412,45 @@ static int iterate(lbfgs_ctx* c) {
                 dmode = LBK_D_TWOLOOP;
             }
         }
-        if (dmode == LBK_D_TWOLOOP && c->unfused) {
-            double rho[MMAX];
-            for (int i = 0; i < h; ++i) rho[i] = 1.0 / c->sy[c->ring[i]];
-            rc = twoloop_unfused(c, rho, gamma);
-            if (rc) return rc;
-            dmode = LBK_D_BUF;
-        } else if (dmode == LBK_D_TWOLOOP && small) {
-            /* one single-workgroup launch: the passes below and the commit at a0 */
+        if (dmode == LBK_D_TWOLOOP) {
             double rho[MMAX];
             const double* Sr[MMAX];
             const double* Yr[MMAX];
-            for (int i = 0; i < h; ++i) {
-                rho[i] = 1.0 / c->sy[c->ring[i]];
-                Sr[i] = c->S[c->ring[i]];
-                Yr[i] = c->Y[c->ring[i]];
-            }
-            const int top = c->ring[h - 1];
-            const int p0_ref = c->sg_valid ? c->sg_ref : -1;
-            c->cur_rho = rho[h - 1];
-            c->cur_gamma = gamma;
-            c->cur_p0 = p0_ref;
-            if (spec_matches(c, h, rho, p0_ref)) { /* already queued behind the last iteration */
-                c->sp_pend = 0;
-                c->cur_epoch = c->sp_epoch;
-                c->cur_spec = 1;
-            } else {
-                rc = spec_drop(c);
+            const int p0_ref = c->sg_valid ? c->sg_ref : -1; /* s_{h-1}.g from the previous commit */
+            ring_view(c, c->ring, h, rho, Sr, Yr);
+            if (c->unfused) {
+                rc = twoloop_unfused(c, rho, gamma);
                 if (rc) return rc;
-                rc = small_launch(c, rho, Sr, Yr, gamma, p0_ref);
-                if (rc) return rc;
-            }
-            /* the next iteration, queued before this one's results are read */
-            rc = spec_next(c, 0.0);
-            if (rc) return rc;
-            c->rho_last = rho[h - 1];
-            c->ref_b_last = REF(SLOT_B0(m) + h - 1, 0);
-            c->ref_a_last = p0_ref >= 0 ? p0_ref : REF(SLOT_P0, 0); /* alpha_{h-1}: s_{h-1} . g */
-            c->s_last_pair = top;
-            c->rc = c->r;
-            small_done = 1;
-        } else if (dmode == LBK_D_TWOLOOP) {
-            int refA[MMAX], refB[MMAX];
-            double rho[MMAX];
-            for (int i = 0; i < h; ++i) rho[i] = 1.0 / c->sy[c->ring[i]];
-            const int top = c->ring[h - 1];
-            if (!ext_obj(c) && c->geo->world == 1 && lbk_twoloop_ok(c->dev, h)) {
-                /* LBFGS_PERSIST=2: the passes below in one persistent launch, same slots */
-                const double* Sr[MMAX];
-                const double* Yr[MMAX];
-                for (int i = 0; i < h; ++i) {
-                    Sr[i] = c->S[c->ring[i]];
-                    Yr[i] = c->Y[c->ring[i]];
-                }
-                DEV(lbk_twoloop_persist(c->dev, h, c->g, c->q, c->r, Sr, Yr, rho, gamma, c->sg_valid ? c->sg_ref : -1,
-                                        SLOT_P0, SLOT_A0, SLOT_B0(m)));
-                refA[h - 1] = c->sg_valid ? c->sg_ref : REF(SLOT_P0, 0);
-                for (int i = h - 2; i >= 0; --i) refA[i] = REF(SLOT_A0 + i, 0);
-                for (int i = 0; i < h; ++i) refB[i] = REF(SLOT_B0(m) + i, 0);
-                c->rc = c->r;
-                c->rho_last = rho[h - 1];
-                c->ref_b_last = refB[h - 1];
-                c->ref_a_last = refA[h - 1];
-                c->s_last_pair = top;
+                dmode = LBK_D_BUF;
             } else {
-                if (c->sg_valid) {
-                    refA[h - 1] = c->sg_ref; /* s_{h-1}.g from the previous commit */
+                if (small) {
+                    /* one single-workgroup launch: the passes of twoloop_passes and the commit at a0 */
+                    c->cur_rho = rho[h - 1];
+                    c->cur_gamma = gamma;
+                    c->cur_p0 = p0_ref;
+                    if (spec_matches(c, h, rho, p0_ref)) { /* already queued behind the last iteration */
+                        c->sp_pend = 0;
+                        c->cur_epoch = c->sp_epoch;
+                        c->cur_spec = 1;
+                    } else {
+                        rc = spec_drop(c);
+                        if (rc) return rc;
+                        rc = small_launch(c, rho, Sr, Yr, gamma, p0_ref);
+                        if (rc) return rc;
+                    }
+                    /* the next iteration, queued before this one's results are read */
+                    rc = spec_next(c, 0.0);
+                    if (rc) return rc;
+                    small_done = 1;
+                } else if (!ext_obj(c) && c->geo->world == 1 && lbk_twoloop_ok(c->dev, h)) {
+                    /* LBFGS_PERSIST=2: the passes of twoloop_passes in one persistent launch, same slots */
+                    DEV(lbk_twoloop_persist(c->dev, h, c->g, c->q, c->r, Sr, Yr, rho, gamma, p0_ref, SLOT_P0, SLOT_A0,
+                                            SLOT_B0(m)));
                 } else {
-                    DEV(lbk_dot(c->dev, c->S[top], c->g, SLOT_P0));
-                    refA[h - 1] = REF(SLOT_P0, 0);
+                    rc = twoloop_passes(c, h, rho, Sr, Yr, gamma, p0_ref);
+                    if (rc) return rc;
                 }
-                /* q and r are updated in place as far as the driver is concerned. The device layer
-                 * keeps the two ends of each vector in place - the tail the alternating walk re-reads
-                 * from the Infinity Cache - and ping-pongs the segments between them through an
-                 * alternate buffer of its own (LBFGS_WORK_SPLIT, DESIGN.md §4 "Split work vector").
-                 * A ping-pong of the whole vectors measured neutral at 1e8 and -8 % at 1e7: it gives
-                 * up the cached ends. */
-                const double* qsrc = c->g;
-                for (int i = h - 2; i >= 0; --i) {
-                    DEV(lbk_axpy_dot(c->dev, c->q, qsrc, c->Y[c->ring[i + 1]], c->S[c->ring[i]], rho[i + 1],
-                                     refA[i + 1], SLOT_A0 + i));
-                    refA[i] = REF(SLOT_A0 + i, 0);
-                    qsrc = c->q;
-                }
-                DEV(lbk_mid(c->dev, c->r, qsrc, c->Y[c->ring[0]], rho[0], gamma, refA[0], SLOT_B0(m)));
-                refB[0] = REF(SLOT_B0(m), 0);
-                for (int i = 0; i + 1 < h; ++i) {
-                    DEV(lbk_axpy2_dot(c->dev, c->r, c->r, c->S[c->ring[i]], c->Y[c->ring[i + 1]], rho[i], refB[i],
-                                      refA[i], SLOT_B0(m) + i + 1));
-                    refB[i + 1] = REF(SLOT_B0(m) + i + 1, 0);
-                }
-                c->rc = c->r;
-                c->rho_last = rho[h - 1];
-                c->ref_b_last = refB[h - 1];
-                c->ref_a_last = refA[h - 1];
-                c->s_last_pair = top;
+                last_update(c, h, rho[h - 1], p0_ref);
             }
         }
     }
@@ -1456,8 +1478,7 @@ static int iterate(lbfgs_ctx* c) {
             rc = materialize_d(c);
             if (rc) return rc;
         }
-        /* the backtracking search's second step, f reduced by the same pass (line_search.cpp:26) */
-        const double cand = (c->batch && c->ls == LBFGS_LS_BACKTRACKING) ? c->a0 * c->K.backtracking_alpha : 0.0;
+        const double cand = first_cand(c); /* a0 is the initial step */
         if (small_done) { /* the commit at a0 ran inside lbk_small_iter */
             rc = small_fetch(c, cslot, tot);
             if (rc) return rc;
@@ -1551,31 +1572,16 @@ static int iterate(lbfgs_ctx* c) {
     }
     const double sy = tot[LBK_C_SY];
     if (sy > 0) { /* :182-191 */
-        const int pair = c->free_pair;
-        if (c->h >= m) {
-            const int oldest = c->ring[0];
-            for (int i = 0; i + 1 < m; ++i) c->ring[i] = c->ring[i + 1];
-            c->ring[m - 1] = pair;
-            c->free_pair = oldest;
-        } else {
-            c->ring[c->h++] = pair;
-            c->free_pair = c->h; /* pool slots 0..h-1 used, h is free */
-        }
-        c->sy[pair] = sy;
-        c->yy[pair] = tot[LBK_C_YY];
+        c->sy[c->free_pair] = sy;
+        c->yy[c->free_pair] = tot[LBK_C_YY];
+        ring_push(m, c->ring, &c->h, &c->free_pair);
         c->sg_valid = !c->unfused;
         c->sg_ref = REF(cslot, LBK_C_SG);
     } else {
         say(c, "Warning: Skipping update, sy = %g\n", sy); /* :192-195 */
         c->sg_valid = 0;
     }
-    /* x = x_new, g = g_new (:197-198) */
-    double* t = c->x;
-    c->x = c->xn;
-    c->xn = t;
-    t = c->g;
-    c->g = c->gn;
-    c->gn = t;
+    swap_iterates(c);
     c->gg = tot[LBK_C_GG];
     c->k++;
     return 0;
@@ -1619,29 +1625,24 @@ static int vf_commit(lbfgs_ctx* c, double alpha, double* tot) {
     return 0;
 }
 
+/* the direction's coefficients (vf_cs, vf_cy, vf_cg) against a row of the basis' products with some
+ * vector v: sum_j cs_j (s_j.v), then sum_j cy_j (y_j.v), then cg (g.v), in that order from 0.0 */
+static double vf_combine(const lbfgs_ctx* c, const double* rowS, const double* rowY, double gval) {
+    double a = 0.0;
+    for (int j = 0; j < c->vf_h; ++j) a = a + c->vf_cs[j] * rowS[j];
+    for (int j = 0; j < c->vf_h; ++j) a = a + c->vf_cy[j] * rowY[j];
+    return a + c->vf_cg * gval;
+}
+
 static int iterate_vf(lbfgs_ctx* c) {
     const int k = c->k, m = c->m, h = c->h;
-    const double gnorm = sqrt(c->gg);
-    int rc = trace_push(c, c->f_cur, gnorm, 1);
+    int rc = iterate_top(c);
     if (rc) return rc;
-    if (c->flags & LBFGS_FLAG_VERBOSE) {
-        printf("Iteration %d, f = %g, |grad| = %g\n", k, c->f_cur, gnorm);
-        fflush(stdout);
-    }
-    if (gnorm < c->tol) {
-        say(c, "Converged!\n");
-        c->status = LBFGS_STATUS_CONVERGED;
-        return 1;
-    }
-    note_h(c);
 
     /* ---- direction in coefficient space (:87-143): d = -(r) with r over the basis ---- */
     c->vf_h = h;
-    for (int j = 0; j < h; ++j) {
-        c->vf_S[j] = c->S[c->ring[j]];
-        c->vf_Y[j] = c->Y[c->ring[j]];
-        c->vf_cs[j] = c->vf_cy[j] = 0.0;
-    }
+    ring_view(c, c->ring, h, NULL, c->vf_S, c->vf_Y);
+    for (int j = 0; j < h; ++j) c->vf_cs[j] = c->vf_cy[j] = 0.0;
     c->vf_cg = -1.0;
     if (!(k == 0 || h == 0)) {
         int bad_rho = 0;
@@ -1680,19 +1681,18 @@ static int iterate_vf(lbfgs_ctx* c) {
             }
         }
     }
-    /* g . d from the Gram row of g */
-    double gd = 0.0;
-    for (int j = 0; j < h; ++j) gd = gd + c->vf_cs[j] * c->Gsg[c->ring[j]];
-    for (int j = 0; j < h; ++j) gd = gd + c->vf_cy[j] * c->Gyg[c->ring[j]];
-    gd = gd + c->vf_cg * c->gg;
+    /* g . d from the Gram row of g, in ring order */
+    double sg[MMAX], yg[MMAX];
+    for (int j = 0; j < h; ++j) {
+        sg[j] = c->Gsg[c->ring[j]];
+        yg[j] = c->Gyg[c->ring[j]];
+    }
+    double gd = vf_combine(c, sg, yg, c->gg);
     if (gd >= 0) { /* :146-153 */
         say(c, "Warning: Not a descent direction, using gradient\n");
         for (int j = 0; j < h; ++j) c->vf_cs[j] = c->vf_cy[j] = 0.0;
         c->vf_cg = -1.0;
-        gd = 0.0;
-        for (int j = 0; j < h; ++j) gd = gd + c->vf_cs[j] * c->Gsg[c->ring[j]];
-        for (int j = 0; j < h; ++j) gd = gd + c->vf_cy[j] * c->Gyg[c->ring[j]];
-        gd = gd + c->vf_cg * c->gg;
+        gd = vf_combine(c, sg, yg, c->gg);
     }
     c->dmode = D_VF;
     c->d_ready = 0;
@@ -1712,10 +1712,7 @@ static int iterate_vf(lbfgs_ctx* c) {
     const int gb = LBK_VF_YB + 2 * c->vf_hb; /* g_new . b_l components */
     for (int j = 0; j < LBK_VF_NA; ++j) c->vf_cand_f[j] = T[LBK_VF_YB + 4 * c->vf_hb + j];
     c->vf_cand_valid = 1;
-    double dgn = 0.0;                        /* g_new . d */
-    for (int j = 0; j < h; ++j) dgn = dgn + c->vf_cs[j] * T[gb + j];
-    for (int j = 0; j < h; ++j) dgn = dgn + c->vf_cy[j] * T[gb + h + j];
-    dgn = dgn + c->vf_cg * T[LBK_VF_GGO];
+    double dgn = vf_combine(c, &T[gb], &T[gb + h], T[LBK_VF_GGO]); /* g_new . d */
     c->sr.have_spec = 1;
     c->sr.spec_a = c->a0;
     c->sr.spec_f = T[LBK_VF_F];
@@ -1733,10 +1730,7 @@ static int iterate_vf(lbfgs_ctx* c) {
         rc = vf_commit(c, alpha, c->vf_tot);
         if (rc) return rc;
         T = c->vf_tot;
-        dgn = 0.0;
-        for (int j = 0; j < h; ++j) dgn = dgn + c->vf_cs[j] * T[gb + j];
-        for (int j = 0; j < h; ++j) dgn = dgn + c->vf_cy[j] * T[gb + h + j];
-        dgn = dgn + c->vf_cg * T[LBK_VF_GGO];
+        dgn = vf_combine(c, &T[gb], &T[gb + h], T[LBK_VF_GGO]);
     }
     T = c->vf_tot;
     c->f_cur = T[LBK_VF_F];
@@ -1761,10 +1755,7 @@ static int iterate_vf(lbfgs_ctx* c) {
             for (int j = 0; j < h; ++j) b = b + c->vf_cy[j] * c->Gyy[GI(c, c->ring[j], rq)];
             dY[q] = b + c->vf_cg * c->Gyg[rq];
         }
-        double dd = 0.0;
-        for (int j = 0; j < h; ++j) dd = dd + c->vf_cs[j] * dS[j];
-        for (int j = 0; j < h; ++j) dd = dd + c->vf_cy[j] * dY[j];
-        dd = dd + c->vf_cg * gd;
+        const double dd = vf_combine(c, dS, dY, gd);
         for (int q = 0; q < h; ++q) {
             const int rq = c->ring[q];
             c->Gss[GI(c, p, rq)] = c->Gss[GI(c, rq, p)] = alpha * dS[q];
@@ -1779,15 +1770,7 @@ static int iterate_vf(lbfgs_ctx* c) {
         c->Gyy[GI(c, p, p)] = T[LBK_VF_YY];
         c->Gsg[p] = alpha * dgn;
         c->Gyg[p] = T[LBK_VF_YG];
-        if (c->h >= m) {
-            const int oldest = c->ring[0];
-            for (int i = 0; i + 1 < m; ++i) c->ring[i] = c->ring[i + 1];
-            c->ring[m - 1] = p;
-            c->free_pair = oldest;
-        } else {
-            c->ring[c->h++] = p;
-            c->free_pair = c->h;
-        }
+        ring_push(m, c->ring, &c->h, &c->free_pair);
     } else {
         say(c, "Warning: Skipping update, sy = %g\n", sy); /* :192-195 */
         for (int q = 0; q < h; ++q) {
@@ -1795,12 +1778,7 @@ static int iterate_vf(lbfgs_ctx* c) {
             c->Gyg[c->ring[q]] = T[gb + h + q];
         }
     }
-    double* t = c->x;
-    c->x = c->xn;
-    c->xn = t;
-    t = c->g;
-    c->g = c->gn;
-    c->gn = t;
+    swap_iterates(c);
     c->gg = T[LBK_VF_GG];
     c->k++;
     return 0;
@@ -1901,22 +1879,29 @@ static int cu_backtracking_wolfe(lbfgs_ctx* c, double gd, double* out) { /* :42-
     return 0;
 }
 
-static int cu_interpolation(lbfgs_ctx* c, double gd, double* out) { /* :149-213 */
+/* The interpolation and Wolfe searches of L-BFGS.cu (line_search.cpp:149-213, :277-368) and of the
+ * variant files (L-BFGS-Interpolation.cu:259-342, L-BFGS-Wolfe.cu:259-349) are one loop each. What
+ * differs comes in and goes out: f_x, the f the tests compare against (a fresh f(x) pass in
+ * L-BFGS.cu, cv_fhost in the variants); f0, the start of f_prev / f_lo (the same f_x, or the
+ * variants' cv_f0); *f_last, the f of the last trial point (the variants' next cv_fhost); *ok, the
+ * variants' line_search_success. */
+static int cu_interpolation(lbfgs_ctx* c, double gd, double f_x, double f0, int floor_every_exit, double* out,
+                            double* f_last, int* ok) {
     const lbfgs_constants* K = &c->K;
-    double f_x, alpha = K->initial_step, alpha_prev = 0.0, f_prev;
-    CU(cu_fx(c, &f_x));
-    f_prev = f_x;
-    int it = 0;
-    while (it++ < 20) {
+    double alpha = K->initial_step, alpha_prev = 0.0, f_prev = f0;
+    int iter;
+    *ok = 0;
+    for (iter = 0; iter < 20; ++iter) {
         double f_new;
         CU(cu_ft(c, alpha, &f_new, NULL));
+        *f_last = f_new;
         if (f_new <= f_x + K->c1 * alpha * gd) {
-            *out = alpha;
-            return 0;
+            *ok = 1;
+            break;
         }
         if (alpha < K->wolfe_interp_min) {
-            *out = K->wolfe_interp_min;
-            return 0;
+            alpha = K->wolfe_interp_min;
+            break;
         }
         if (alpha_prev > 0) {
             const double delta = alpha - alpha_prev;
@@ -1931,10 +1916,12 @@ static int cu_interpolation(lbfgs_ctx* c, double gd, double* out) { /* :149-213 
             alpha = lbk_search_quad(alpha, f_new, gd, f_x);
             if (alpha < 0.1 * K->initial_step || alpha > 0.9 * K->initial_step) alpha = K->initial_step * 0.5;
         }
-        alpha_prev = alpha;
+        alpha_prev = alpha; /* after the update (L-BFGS-Interpolation.cu:335) */
         f_prev = f_new;
     }
-    *out = alpha < 1e-4 ? 0.5 : alpha;
+    /* the floor: only after 20 trials in L-BFGS.cu's search, on every exit in the variant's (:339-342) */
+    if ((iter == 20 || floor_every_exit) && alpha < 1e-4) alpha = 0.5;
+    *out = alpha;
     return 0;
 }
 
@@ -1966,24 +1953,24 @@ static double cu_safe_cubic(double a0, double a1, double p0, double dp0, double 
     return (lo < mn) ? mn : lo;          /* std::max(lo, .) */
 }
 
-static int cu_wolfe(lbfgs_ctx* c, double gd, double* out) { /* :277-368 */
+static int cu_wolfe(lbfgs_ctx* c, double gd, double f_x, double f0, double* out, double* f_last, int* ok) {
     const lbfgs_constants* K = &c->K;
-    double f_x, alpha = K->initial_step;
-    CU(cu_fx(c, &f_x));
-    double alpha_lo = 0.0, alpha_hi = INFINITY, f_lo = f_x, dphi_lo = gd;
+    double alpha = K->initial_step, alpha_lo = 0.0, alpha_hi = INFINITY, f_lo = f0, dphi_lo = gd;
+    *ok = 0;
     for (int iter = 0; iter < 20; ++iter) {
         double f_new;
         CU(cu_ft(c, alpha, &f_new, NULL));
+        *f_last = f_new;
         if (f_new > f_x + K->c1 * alpha * gd || (f_new >= f_lo && iter > 0)) {
             alpha_hi = alpha;
             alpha = cu_safe_cubic(alpha_lo, alpha_hi, f_lo, dphi_lo, f_new, (f_new - f_x - gd * alpha) / (alpha * alpha));
-            continue;
+            continue; /* past the WOLFE_INTERP_MIN floor */
         }
         double fg, dphi_new;
         CU(cu_ft(c, alpha, &fg, &dphi_new)); /* grad(x_new) . d */
         if (fabs(dphi_new) <= -K->c2 * gd) {
-            *out = alpha;
-            return 0;
+            *ok = 1;
+            break;
         }
         if (dphi_new >= 0) {
             alpha_hi = alpha;
@@ -1998,8 +1985,8 @@ static int cu_wolfe(lbfgs_ctx* c, double gd, double* out) { /* :277-368 */
                 alpha = cu_safe_cubic(alpha_lo, alpha_hi, f_lo, dphi_lo, f_new, dphi_new);
         }
         if (alpha < K->wolfe_interp_min) {
-            *out = K->wolfe_interp_min;
-            return 0;
+            alpha = K->wolfe_interp_min;
+            break;
         }
     }
     *out = alpha;
@@ -2009,7 +1996,8 @@ static int cu_wolfe(lbfgs_ctx* c, double gd, double* out) { /* :277-368 */
 /* ------------------------------------------------------------------------------------------
  * LBFGS_FLAG_CUDA_VARIANT: the inline searches of the four variant files. Each trial transfers
  * x + a d to the host copy x_host, so f(x_host) at the next iteration is the f of the last trial
- * point transferred (cv_fhost), not f(x). ok = the search's line_search_success.
+ * point transferred (cv_fhost), not f(x). ok = the search's line_search_success. Interpolation
+ * and Wolfe are the loops above; the two backtracking searches are the files' own.
  * ---------------------------------------------------------------------------------------- */
 static int cv_backtracking(lbfgs_ctx* c, double gd, double* out) { /* L-BFGS-Backtracking.cu:293-341 */
     const double C1 = 1e-4, TOL = 1e-10; /* :153-156, the file's own constants */
@@ -2025,87 +2013,6 @@ static int cv_backtracking(lbfgs_ctx* c, double gd, double* out) { /* L-BFGS-Bac
         }
     }
     *out = step;
-    return 0;
-}
-
-static int cv_interpolation(lbfgs_ctx* c, double gd, double* out, int* ok) { /* L-BFGS-Interpolation.cu:259-342 */
-    const lbfgs_constants* K = &c->K;
-    const double f_x = c->cv_fhost;
-    double alpha = K->initial_step, alpha_prev = 0.0, f_prev = c->cv_f0;
-    *ok = 0;
-    for (int iter = 0; iter < 20; ++iter) {
-        double f_new;
-        CU(cu_ft(c, alpha, &f_new, NULL));
-        c->cv_fhost = f_new;
-        if (f_new <= f_x + K->c1 * alpha * gd) {
-            *ok = 1;
-            break;
-        }
-        if (alpha < K->wolfe_interp_min) {
-            alpha = K->wolfe_interp_min;
-            break;
-        }
-        if (alpha_prev > 0) {
-            const double delta = alpha - alpha_prev;
-            if (fabs(delta) < 1e-10) {
-                alpha *= 0.5;
-            } else {
-                const double ga = (f_new - f_x - gd * alpha) / (alpha * alpha);
-                double next = lbk_search_cubic(alpha_prev, alpha, f_prev, gd, f_new, ga);
-                if (next < 0.1 * alpha_prev || next > 0.9 * alpha_prev) next = alpha_prev * 0.5;
-                alpha = next;
-            }
-        } else {
-            double next = lbk_search_quad(alpha, f_new, gd, f_x);
-            if (next < 0.1 * K->initial_step || next > 0.9 * K->initial_step) next = K->initial_step * 0.5;
-            alpha = next;
-        }
-        alpha_prev = alpha; /* after the update (:335) */
-        f_prev = f_new;
-    }
-    if (alpha < 1e-4) alpha = 0.5; /* :339-342 */
-    *out = alpha;
-    return 0;
-}
-
-static int cv_wolfe(lbfgs_ctx* c, double gd, double* out, int* ok) { /* L-BFGS-Wolfe.cu:259-349 */
-    const lbfgs_constants* K = &c->K;
-    const double f_x = c->cv_fhost;
-    double alpha = K->initial_step, alpha_lo = 0.0, alpha_hi = INFINITY, f_lo = c->cv_f0, dphi_lo = gd;
-    *ok = 0;
-    for (int iter = 0; iter < 20; ++iter) {
-        double f_new;
-        CU(cu_ft(c, alpha, &f_new, NULL));
-        c->cv_fhost = f_new;
-        if (f_new > f_x + K->c1 * alpha * gd || (f_new >= f_lo && iter > 0)) {
-            alpha_hi = alpha;
-            alpha = cu_safe_cubic(alpha_lo, alpha_hi, f_lo, dphi_lo, f_new, (f_new - f_x - gd * alpha) / (alpha * alpha));
-            continue; /* past the WOLFE_INTERP_MIN floor */
-        }
-        double fg, dphi_new;
-        CU(cu_ft(c, alpha, &fg, &dphi_new)); /* grad(x_host) . d */
-        if (fabs(dphi_new) <= -K->c2 * gd) {
-            *ok = 1;
-            break;
-        }
-        if (dphi_new >= 0) {
-            alpha_hi = alpha;
-            alpha = cu_safe_cubic(alpha_lo, alpha_hi, f_lo, dphi_lo, f_new, dphi_new);
-        } else {
-            alpha_lo = alpha;
-            f_lo = f_new;
-            dphi_lo = dphi_new;
-            if (alpha_hi == INFINITY)
-                alpha *= 2;
-            else
-                alpha = cu_safe_cubic(alpha_lo, alpha_hi, f_lo, dphi_lo, f_new, dphi_new);
-        }
-        if (alpha < K->wolfe_interp_min) {
-            alpha = K->wolfe_interp_min;
-            break;
-        }
-    }
-    *out = alpha;
     return 0;
 }
 
@@ -2197,8 +2104,10 @@ static int iterate_cuda(lbfgs_ctx* c) {
         CU(cu_dot(c, c->g, c->d, &gd));
         switch (c->ls) {
             case LBFGS_LS_BACKTRACKING: CU(cv_backtracking(c, gd, &step)); break;
-            case LBFGS_LS_INTERPOLATION: CU(cv_interpolation(c, gd, &step, &ok)); break;
-            case LBFGS_LS_WOLFE: CU(cv_wolfe(c, gd, &step, &ok)); break;
+            case LBFGS_LS_INTERPOLATION:
+                CU(cu_interpolation(c, gd, c->cv_fhost, c->cv_f0, 1, &step, &c->cv_fhost, &ok));
+                break;
+            case LBFGS_LS_WOLFE: CU(cu_wolfe(c, gd, c->cv_fhost, c->cv_f0, &step, &c->cv_fhost, &ok)); break;
             default: CU(cv_backtracking_wolfe(c, gd, &step, &ok)); break;
         }
         say(c, "alpha: %g\n", step);
@@ -2211,11 +2120,19 @@ static int iterate_cuda(lbfgs_ctx* c) {
             return 1;
         }
     } else { /* the line search with the iteration-0 gradient (:199, :293) */
+        double fx, f_last; /* f(x): a pass of its own; the last trial's f and ok are the variants' */
+        int ok;
         CU(cu_dot(c, c->g0c, c->d, &gd));
         switch (c->ls) {
             case LBFGS_LS_BACKTRACKING: CU(cu_backtracking(c, gd, &step)); break;
-            case LBFGS_LS_INTERPOLATION: CU(cu_interpolation(c, gd, &step)); break;
-            case LBFGS_LS_WOLFE: CU(cu_wolfe(c, gd, &step)); break;
+            case LBFGS_LS_INTERPOLATION:
+                CU(cu_fx(c, &fx));
+                CU(cu_interpolation(c, gd, fx, fx, 0, &step, &f_last, &ok));
+                break;
+            case LBFGS_LS_WOLFE:
+                CU(cu_fx(c, &fx));
+                CU(cu_wolfe(c, gd, fx, fx, &step, &f_last, &ok));
+                break;
             default: CU(cu_backtracking_wolfe(c, gd, &step)); break;
         }
         if (step < 1e-10) { /* :295-306 */
@@ -2234,14 +2151,7 @@ static int iterate_cuda(lbfgs_ctx* c) {
     DEV(lbk_elementwise(c->dev, 3, c->Y[sl], c->gn, c->g, -1.0));
     CU(cu_dot(c, c->S[sl], c->Y[sl], &c->sy[sl])); /* the next iteration's ddot(s, y) and ddot(y, y) */
     CU(cu_dot(c, c->Y[sl], c->Y[sl], &c->yy[sl]));
-    {
-        double* tp = c->x; /* :335-340 */
-        c->x = c->xn;
-        c->xn = tp;
-        tp = c->g;
-        c->g = c->gn;
-        c->gn = tp;
-    }
+    swap_iterates(c); /* :335-340 */
     c->commits++;
     c->f_cur = t[0];
     c->gg = t[1];
@@ -2252,9 +2162,7 @@ static int iterate_cuda(lbfgs_ctx* c) {
         CU(trace_push(c, t[0], norm_g, 1));
         c->tr_a[c->tr_len - 1] = step;
     }
-    const int h = k + 1 < m ? k + 1 : m; /* ring slots written */
-    if (c->h_min < 0 || h < c->h_min) c->h_min = h;
-    if (h > c->h_max) c->h_max = h;
+    note_h(c, k + 1 < m ? k + 1 : m); /* ring slots written */
     c->k++;
     if (norm_g <= c->tol) { /* :353-357 */
         say(c, "Convergence achieved at iteration %d\n", k);
@@ -2279,6 +2187,20 @@ static int export_device(lbfgs_ctx* c, double* dst_dev, const double* src) {
     DEV(lbk_elementwise(c->dev, 0, dst_dev, src, NULL, 1.0));
     DEVNC(lbk_sync(c->dev)); /* complete on return */
     return 0;
+}
+
+/* an on/off environment switch: unset = dflt, else its integer value != 0 */
+static int env_switch(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) != 0 : dflt;
+}
+
+/* the line-search constants of a solve or a standalone search: the caller's, or the defaults */
+static void set_constants(lbfgs_ctx* c, const lbfgs_constants* k) {
+    if (k)
+        c->K = *k;
+    else
+        lbfgs_constants_default(&c->K);
 }
 
 /* x0_dev != 0: x0 is a caller-owned device buffer (lbfgs_solver_init_device) */
@@ -2309,22 +2231,14 @@ static int solver_init_at(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, 
         if (rc) return rc;
     }
     /* speculative next iteration at small n (LBFGS_SPEC=0: off; the same iterates either way) */
-    c->spec_on = 1;
-    {
-        const char* e = getenv("LBFGS_SPEC");
-        if (e) c->spec_on = atoi(e) != 0;
-    }
+    c->spec_on = env_switch("LBFGS_SPEC", 1);
     c->cur_epoch = 0;
     c->cur_spec = 0;
     c->sp_adopted = c->sp_dropped = 0;
     c->search_launches = c->search_commits = 0;
     c->unfused = (flags & LBFGS_FLAG_UNFUSED) != 0;
     c->many_passes = c->tl_search = 0;
-    c->batch = 1;
-    {
-        const char* e = getenv("LBFGS_BATCH");
-        if (e) c->batch = atoi(e) != 0;
-    }
+    c->batch = env_switch("LBFGS_BATCH", 1);
     if (c->unfused && (objective >= LBFGS_OBJ_HOST || c->geo->world != 1)) return LBFGS_ERR_BAD_ARG;
     c->vf = (flags & LBFGS_FLAG_VECTOR_FREE) != 0;
     if (c->vf) {
@@ -2350,10 +2264,7 @@ static int solver_init_at(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, 
     }
     c->obj = objective;
     c->ls = line_search;
-    if (k)
-        c->K = *k;
-    else
-        lbfgs_constants_default(&c->K);
+    set_constants(c, k);
     c->tol = tolerance;
     c->flags = flags;
     c->k = 0;
@@ -2626,25 +2537,16 @@ int lbfgs_dev_twoloop(lbfgs_ctx* c, const double* g, const double* const* S, con
         DEV(lbk_dot(c->dev, c->Y[i], c->Y[i], SLOT_MISC(m)));
         DEVNC(lbk_fetch(c->dev, SLOT_MISC(m), 1, &c->yy[i]));
     }
-    int refA[MMAX], refB[MMAX];
+    /* the solver's own passes over the identity ring, no s_{h-1}.g carried over, then k_last */
     double rho[MMAX];
-    for (int i = 0; i < h; ++i) rho[i] = 1.0 / c->sy[i];
-    const double gamma = c->sy[h - 1] / c->yy[h - 1];
-    DEV(lbk_dot(c->dev, c->S[h - 1], c->g, SLOT_P0));
-    refA[h - 1] = REF(SLOT_P0, 0);
-    const double* qsrc = c->g;
-    for (int i = h - 2; i >= 0; --i) {
-        DEV(lbk_axpy_dot(c->dev, c->q, qsrc, c->Y[i + 1], c->S[i], rho[i + 1], refA[i + 1], SLOT_A0 + i));
-        refA[i] = REF(SLOT_A0 + i, 0);
-        qsrc = c->q;
-    }
-    DEV(lbk_mid(c->dev, c->r, qsrc, c->Y[0], rho[0], gamma, refA[0], SLOT_B0(m)));
-    refB[0] = REF(SLOT_B0(m), 0);
-    for (int i = 0; i + 1 < h; ++i) {
-        DEV(lbk_axpy2_dot(c->dev, c->r, c->r, c->S[i], c->Y[i + 1], rho[i], refB[i], refA[i], SLOT_B0(m) + i + 1));
-        refB[i + 1] = REF(SLOT_B0(m) + i + 1, 0);
-    }
-    DEV(lbk_last(c->dev, c->d, c->r, c->S[h - 1], c->g, rho[h - 1], refB[h - 1], refA[h - 1], SLOT_LAST(m)));
+    const double* Sr[MMAX];
+    const double* Yr[MMAX];
+    ring_view(c, c->ring, h, rho, Sr, Yr);
+    const int rc = twoloop_passes(c, h, rho, Sr, Yr, c->sy[h - 1] / c->yy[h - 1], -1);
+    if (rc) return rc;
+    last_update(c, h, rho[h - 1], -1);
+    DEV(lbk_last(c->dev, c->d, c->rc, c->S[c->s_last_pair], c->g, c->rho_last, c->ref_b_last, c->ref_a_last,
+                 SLOT_LAST(m)));
     double gd;
     DEVNC(lbk_fetch(c->dev, SLOT_LAST(m), 1, &gd));
     if (gd_out) *gd_out = gd;
@@ -2673,11 +2575,7 @@ int lbfgs_line_search(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int 
     c->cb_f = c->cb_g = 0;
     c->inited = 0;
     c->unfused = 0;
-    c->batch = 1;
-    {
-        const char* e = getenv("LBFGS_BATCH");
-        if (e) c->batch = atoi(e) != 0;
-    }
+    c->batch = env_switch("LBFGS_BATCH", 1);
     c->sr.have_cand = 0;
     c->sr.tc_n = 0;
     c->trial_passes = 0;
@@ -2685,10 +2583,7 @@ int lbfgs_line_search(lbfgs_ctx* c, int objective, const lbfgs_host_fn* cb, int 
     c->cuda = 0;
     c->obj = objective;
     c->ls = line_search;
-    if (k)
-        c->K = *k;
-    else
-        lbfgs_constants_default(&c->K);
+    set_constants(c, k);
     const int m = c->m;
     DEVNC(lbk_upload(c->dev, c->x, x));
     DEVNC(lbk_upload(c->dev, c->d, d));
