@@ -108,6 +108,93 @@ __global__ __launch_bounds__(LB_BLOCK) void k_reduce_groups(const double* __rest
     group_tree<1, false>(partials, gseg0, gseg0, nseg, LBK_SEG_PER_GROUP, slot + g, hslot + g, lds);
 }
 
+// The same total of every row of a table in one launch (lbfgs_reduce_rows): within
+// the batched solver's limits (n <= 32768: L = 512, at most 64 segments) a row is one workgroup's
+// work and needs no second launch. Workgroup p takes row p; an inactive row's workgroup returns at
+// once. The order is k_reduce_segments' for L = 512 followed by batch_pass's stage 2:
+//   - segment s = [512 s, min(512 (s + 1), n)), wave w row w of it (128 elements), lane l elements
+//     2l, 2l + 1 of that row; acc = 0.0, then fma(a.x, b.x, acc), fma(a.y, b.y, acc) for a dot,
+//     acc + a.x, acc + a.y for a sum; an element at or beyond n contributes nothing;
+//   - wave_sum; lane 0 of wave w leaves its value of segment s in LDS; the segment partial is
+//     ((w0 + w1) + (w2 + w3));
+//   - wave 0, lane j: the partial of segment j for j < nseg, else 0.0; wave_sum(p) + 0.0 is group 0
+//     (the tree's levels above 64 add 0.0), and the 7 empty groups add 0.0 each; thread 0 stores.
+// Nothing outside [0, n) of a row is read: full segments lie inside it and their loads are
+// unconditional, four segments of them in flight per lane before the first wave_sum (accumulation
+// stays per segment); the last, partial segment tests every element. 16-byte loads when this row's
+// pointers are 16-byte aligned (with an odd lda the rows alternate), two 8-byte loads otherwise: a
+// branch uniform in the workgroup. Plain cached loads: a row is at most 256 KiB and was just written.
+template <bool DOT, bool VEC>
+__device__ __forceinline__ void reduce_row_segments(const double* __restrict__ a, const double* __restrict__ b, int n,
+                                                    double (&ws)[4][64]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nfull = n >> 9;
+    const int o = w * 128 + 2 * lane;  // of this lane's pair within a segment
+    int s = 0;
+    for (; s + 4 <= nfull; s += 4) {
+        double2 ra[4], rb[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            ra[j] = ld_pair<VEC, false>(a + (s + j) * 512 + o);
+            rb[j] = DOT ? ld_pair<VEC, false>(b + (s + j) * 512 + o) : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double v = wave_sum(acc_pair<DOT>(ra[j], rb[j], 0.0, true, true));
+            if (lane == 0) ws[w][s + j] = v;
+        }
+    }
+    for (; s < nfull; ++s) {
+        const double2 ra = ld_pair<VEC, false>(a + s * 512 + o);
+        const double2 rb = DOT ? ld_pair<VEC, false>(b + s * 512 + o) : make_double2(0.0, 0.0);
+        const double v = wave_sum(acc_pair<DOT>(ra, rb, 0.0, true, true));
+        if (lane == 0) ws[w][s] = v;
+    }
+    if (n & 511) {  // the partial segment: a test per element
+        const int i = s * 512 + o;
+        const bool v0 = i < n, v1 = i + 1 < n;
+        double2 ra = make_double2(0.0, 0.0), rb = make_double2(0.0, 0.0);
+        if (v1) {
+            ra = ld_pair<VEC, false>(a + i);
+            if (DOT) rb = ld_pair<VEC, false>(b + i);
+        } else if (v0) {
+            ra.x = a[i];
+            if (DOT) rb.x = b[i];
+        }
+        const double v = wave_sum(acc_pair<DOT>(ra, rb, 0.0, v0, v1));
+        if (lane == 0) ws[w][s] = v;
+    }
+}
+
+template <bool DOT>
+__global__ __launch_bounds__(LB_BLOCK) void k_reduce_rows(const double* __restrict__ a, int64_t lda,
+                                                          const double* __restrict__ b, int64_t ldb,
+                                                          const int* __restrict__ active, int n,
+                                                          double* __restrict__ out) {
+    __shared__ double ws[4][64];  // [wave][segment]
+    const int64_t p = blockIdx.x;
+    if (active && active[p] == 0) return;
+    a += p * lda;
+    if (DOT) b += p * ldb;
+    const uintptr_t bits = (uintptr_t)a | (DOT ? (uintptr_t)b : 0);
+    if ((bits & 15) == 0)
+        reduce_row_segments<DOT, true>(a, b, n, ws);
+    else
+        reduce_row_segments<DOT, false>(a, b, n, ws);
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x, nseg = (n + 511) >> 9;
+        const double q = lane < nseg ? (ws[0][lane] + ws[1][lane]) + (ws[2][lane] + ws[3][lane]) : 0.0;
+        const double q0 = wave_sum(q) + 0.0;  // group 0: the tree's levels above 64 add 0.0
+        if (lane == 0) {
+            double tt = q0;
+#pragma unroll
+            for (int g = 1; g < LBK_GROUPS; ++g) tt = tt + 0.0;
+            out[p] = tt;
+        }
+    }
+}
+
 }  // namespace
 
 struct lbfgs_reducer {
@@ -202,6 +289,30 @@ int lbfgs_reducer_dot(lbfgs_reducer* r, const double* a_dev, const double* b_dev
     for (int g = 1; g < LBK_GROUPS; ++g) t = t + r->hslot[g];
     *out_host = t;
     return 0;
+}
+
+int lbfgs_reduce_rows(int device, int64_t n, int batch, const double* a_dev, int64_t lda, const double* b_dev,
+                      int64_t ldb, const int* active_dev, double* out_dev, void* hip_stream) {
+    // refusals first, before any HIP call: a machine without a device gives them too
+    if (device < 0 || n < 1 || n > 32768 || batch < 1 || !a_dev || !out_dev || lda < n) return LBFGS_ERR_BAD_ARG;
+    if (((uintptr_t)a_dev | (uintptr_t)b_dev | (uintptr_t)out_dev) & 7) return LBFGS_ERR_BAD_ARG;
+    if (b_dev && ldb != 0 && ldb < n) return LBFGS_ERR_BAD_ARG;
+    // the calling thread's device is left as it was (stateless: the caller may be torch on another one)
+    int prev = device;
+    if (hipGetDevice(&prev) != hipSuccess || (prev != device && hipSetDevice(device) != hipSuccess)) {
+        (void)hipGetLastError();
+        return LBFGS_ERR_HIP;
+    }
+    const hipStream_t st = (hipStream_t)hip_stream;
+    const dim3 grid((unsigned)batch), block(LB_BLOCK);
+    if (b_dev)
+        hipLaunchKernelGGL(k_reduce_rows<true>, grid, block, 0, st, a_dev, lda, b_dev, ldb, active_dev, (int)n, out_dev);
+    else
+        hipLaunchKernelGGL(k_reduce_rows<false>, grid, block, 0, st, a_dev, lda, b_dev, ldb, active_dev, (int)n,
+                           out_dev);
+    const bool ok = hipGetLastError() == hipSuccess;
+    if (prev != device) (void)hipSetDevice(prev);
+    return ok ? 0 : LBFGS_ERR_HIP;
 }
 
 }  // extern "C"

@@ -194,6 +194,7 @@ def lib():
     L.lbfgs_reducer_destroy.argtypes = [vp]
     L.lbfgs_reducer_destroy.restype = None
     L.lbfgs_reducer_dot.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double)]
+    L.lbfgs_reduce_rows.argtypes = [C.c_int, C.c_int64, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, vp, vp]
     _lib = L
     return L
 
@@ -216,7 +217,7 @@ EXPORTED_SYMBOLS = [
     "lbfgs_batch_minimize_device", "lbfgs_batch_set_dense_quadratics_device",
     "lbfgs_batch_ragged_plan", "lbfgs_batch_create_ragged", "lbfgs_batch_sizes", "lbfgs_batch_set_device_objective",
     "lbfgs_set_device_objective", "lbfgs_minimize_device", "lbfgs_solver_init_device", "lbfgs_get_x_device",
-    "lbfgs_reducer_create", "lbfgs_reducer_destroy", "lbfgs_reducer_dot",
+    "lbfgs_reducer_create", "lbfgs_reducer_destroy", "lbfgs_reducer_dot", "lbfgs_reduce_rows",
 ]
 PEER_HANDLE_BYTES = 64
 BACKENDS = {0: "single", 1: "rccl", 2: "xgmi", 3: "host-group"}
@@ -453,7 +454,10 @@ class Batch:
         when fn has returned. Every problem's result is bit for bit what Context.set_device_objective(
         eager_grad=True) + Context.minimize_device("device") gives for it alone with the same f and g;
         f_calls / grad_calls are the rounds the problem was active in. Uniform batches only. An
-        exception raised by fn ends the solve and is re-raised by minimize. fn = None clears."""
+        exception raised by fn ends the solve and is re-raised by minimize. fn = None clears.
+        For F in the solver's canonical order (reproducible, the bits of Reducer.sum per row) fn forms it
+        with reduce_rows(T, active=active), T the (batch, n) table of per-element terms: one launch for
+        all rows and no host wait, where Reducer.sum is two launches and a host wait per row."""
         if fn is None:
             rc = lib().lbfgs_batch_set_device_objective(self.h, None)
             self._dev_cb = None
@@ -799,7 +803,9 @@ class Reducer:
     tensors may sit at any storage offset; nothing outside them is read. Runs on torch's current
     stream (the null stream orders nothing against the library's own non-blocking streams, so when
     that is the current one it is synchronised first and the reducer's own stream is used); the
-    value is complete on return."""
+    value is complete on return. One vector per call, two launches and a host wait: inside a batch
+    callback (Batch.set_device_objective) use the row form, reduce_rows, which gives the same bits for
+    every row of a table in one launch and leaves them on the device."""
 
     def __init__(self, n, device=0):
         _torch()
@@ -849,6 +855,75 @@ class Reducer:
 
     def sum(self, t):
         return self.dot(t, None)
+
+
+REDUCE_ROWS_NMAX = 32768  # the batched solver's limit: L = 512, at most 64 segments
+
+
+def reduce_rows(a, b=None, active=None, out=None):
+    """The canonical fixed-order sum of every row of a table in one launch (lbfgs_reduce_rows): out[p] =
+    sum_i a[p, i] * b[p, i] (b = None: of a[p, i]), bit for bit Reducer.dot / Reducer.sum of that row.
+    The form for a batch callback (Batch.set_device_objective): one launch whatever the batch, the
+    result left in device memory, no host wait.
+
+    a: a 2-D float64 CUDA tensor (B, n) with stride(1) == 1 and stride(0) >= n, at any storage offset,
+    n <= 32768. b: None, the same kind of tensor, or a 1-D contiguous (n,) tensor shared by every row.
+    active: None or a (B,) int32 contiguous CUDA tensor (the view a batch callback receives); a row with
+    0 is skipped and its out[p] is not written. out: None (a new (B,) tensor filled with NaN, so that
+    skipped rows are recognisable) or a (B,) contiguous float64 CUDA tensor. Returns out. Runs on torch's
+    current stream of the tensors' device, the null stream included, and does not synchronise.
+    ValueError for anything else, before anything is launched; LbfgsError with .rc on a nonzero return."""
+    torch = _torch()
+
+    def f64(t, what):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
+            raise ValueError(f"reduce_rows: {what}: a float64 CUDA tensor is required")
+
+    f64(a, "a")
+    if a.dim() != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("reduce_rows: a: a 2-D tensor (B, n) with B >= 1 and n >= 1 is required")
+    B, n = a.shape
+    dev = a.device
+    if n > REDUCE_ROWS_NMAX:
+        raise ValueError(f"reduce_rows: n = {n} is above {REDUCE_ROWS_NMAX} (a longer row uses Reducer)")
+
+    def rows(t, what):  # the row stride of a (B, n) table with unit inner stride
+        if t.shape != (B, n) or t.stride(1) != 1 and n > 1 or t.stride(0) < n and B > 1:
+            raise ValueError(f"reduce_rows: {what}: shape ({B}, {n}) with stride(1) == 1 and stride(0) >= n is required")
+        return t.stride(0) if B > 1 else n
+
+    lda = rows(a, "a")
+    ldb = 0
+    if b is not None:
+        f64(b, "b")
+        if b.device != dev:
+            raise ValueError("reduce_rows: b: on another device than a")
+        if b.dim() == 1:
+            if b.shape != (n,) or not b.is_contiguous():
+                raise ValueError(f"reduce_rows: b: a shared b is a contiguous 1-D tensor of {n} elements")
+        elif b.dim() == 2:
+            ldb = rows(b, "b")
+        else:
+            raise ValueError("reduce_rows: b: a 1-D or 2-D tensor is required")
+    if active is not None:
+        if not (isinstance(active, torch.Tensor) and active.is_cuda and active.dtype == torch.int32 and
+                active.shape == (B,) and active.is_contiguous() and active.device == dev):
+            raise ValueError(f"reduce_rows: active: a contiguous int32 CUDA tensor of shape ({B},) on a's device is required")
+    if out is None:
+        out = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
+    else:
+        f64(out, "out")
+        if out.shape != (B,) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"reduce_rows: out: a contiguous tensor of shape ({B},) on a's device is required")
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    rc = lib().lbfgs_reduce_rows(index, n, B, a.data_ptr(), lda, b.data_ptr() if b is not None else None, ldb,
+                                 active.data_ptr() if active is not None else None, out.data_ptr(),
+                                 torch.cuda.current_stream(index).cuda_stream or None)
+    if rc != 0:
+        e = LbfgsError(f"lbfgs_reduce_rows failed ({rc})")
+        e.rc = rc
+        raise e
+    return out
 
 
 class Context:

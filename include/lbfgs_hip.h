@@ -547,6 +547,21 @@ void lbfgs_reducer_destroy(lbfgs_reducer* r);
  * valid on return */
 int lbfgs_reducer_dot(lbfgs_reducer* r, const double* a_dev, const double* b_dev, void* hip_stream,
                       double* out_host);
+/* The row form, for a batch callback (lbfgs_batch_device_eval) that forms f of every row: out_dev[p] =
+ * the same canonical sum over i < n of a_p[i] * b_p[i] (b_dev == NULL: of a_p[i]), bit for bit what
+ * lbfgs_reducer_dot returns for that row alone. Row p of a is a_dev + p*lda (lda >= n), row p of b is
+ * b_dev + p*ldb (ldb >= n, or ldb == 0: one b shared by every row). active_dev (nullable): batch ints
+ * in device memory; a row with 0 is skipped, its out_dev[p] not written. 1 <= n <= 32768, the batched
+ * solver's limit; batch >= 1 (a longer row uses lbfgs_reducer_dot). The buffers are caller-owned,
+ * unpadded, 8-byte aligned and no more; nothing outside [0, n) of a row is read, nothing but
+ * out_dev[p] of active rows is written; out_dev overlapping an input is the caller's error.
+ * Stateless: ONE kernel enqueued on hip_stream (NULL = the null stream) and no more: no
+ * synchronisation, allocation or copy, so the result is ordered on that stream like any kernel's
+ * and the call is legal inside a stream capture. Returns 0, LBFGS_ERR_HIP for a launch failure, or
+ * LBFGS_ERR_BAD_ARG, decided before any HIP call: n or batch out of range, a negative device, a null
+ * a_dev or out_dev, a pointer that is not 8-byte aligned, lda < n, ldb neither 0 nor >= n with b given. */
+int lbfgs_reduce_rows(int device, int64_t n, int batch, const double* a_dev, int64_t lda, const double* b_dev,
+                      int64_t ldb, const int* active_dev, double* out_dev, void* hip_stream);
 
 /* ---- line search alone (line_search.h:10-26 on the GPU) -------------------------------- */
 /* Step size along d from x (gradient g at x) by one of the four line searches, every trial on
