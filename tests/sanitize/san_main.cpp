@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
 #include <functional>
 #include <string>
 #include <vector>
@@ -203,6 +204,85 @@ static void cuda_paths() {
                     if (st >= 0) compare(tag, c, st, x, res, oracle(obj, ls, n, m, maxit, x0, nullptr, nullptr, nullptr, cuda, tol));
                     lbfgs_ctx_destroy(c);
                 }
+}
+
+// Histories of 17 and 64 pairs (MMAX): the driver's MMAX-sized arrays, the ring of m + 1 pairs and its
+// rotation, the slots up to SLOT_MISC(64), and the move in mid-solve, at the first iteration with 17
+// pairs, from the single-launch iteration (with the next one queued) to the launch sequence while the
+// device-resident searches go on. Rosenbrock from the start of tests/hist_cases.py's SINGLE_LONG, every
+// line search, modes 0, 2, 3, 4 and 5 of device_objectives(); one run of each CUDA path at m = 64.
+static void long_history() {
+    const int64_t sizes[] = {3, 1537};
+    const int hist[] = {17, 64}, modes[] = {0, 2, 3, 4, 5}, maxit = 80;
+    const double tol = 1e-7;
+    int64_t adopted = 0, searches = 0;
+    const std::clock_t t0 = std::clock();
+    for (int64_t n : sizes)
+        for (int m : hist)
+            for (int ls = 0; ls < 4; ++ls) {
+                const auto x0 = x0_for(n, 1);
+                const OracleRun o = oracle(ORC_OBJ_ROSENBROCK, ls, n, m, maxit, x0, nullptr, nullptr, nullptr, 0, tol);
+                for (int mode : modes) {
+                    setenv("LBFGS_DOUBLE_SMALL", mode == 3 || mode == 4 ? "1" : "0", 1);
+                    setenv("LBFGS_SPEC", mode == 4 ? "0" : "1", 1);
+                    setenv("LBFGS_DOUBLE_TWOLOOP", mode == 5 ? "1" : "0", 1);
+                    lbfgs_ctx* c = nullptr;
+                    EXPECT(lbfgs_ctx_create(&c, n, m, 0) == 0, "create n=%lld m=%d", (long long)n, m);
+                    if (!c) continue;
+                    std::vector<double> x(n);
+                    lbfgs_result res;
+                    const unsigned flags = LBFGS_FLAG_QUIET | LBFGS_FLAG_TRACE | (mode == 2 ? LBFGS_FLAG_UNFUSED : 0u);
+                    const int st = lbfgs_minimize(c, LBFGS_OBJ_ROSENBROCK, nullptr, ls, nullptr, x0.data(), x.data(), maxit,
+                                                  tol, flags, &res);
+                    char tag[96];
+                    std::snprintf(tag, sizeof tag, "long history n=%lld m=%d ls=%d mode=%d", (long long)n, m, ls, mode);
+                    EXPECT(st >= 0, "%s: %d %s", tag, st, lbfgs_last_error(c));
+                    if (st >= 0) compare(tag, c, st, x, res, o);
+                    // at n = 1537 every run takes its 80 iterations and fills the ring
+                    EXPECT(n < 10 || (res.iterations == maxit && res.h_max == m), "%s: %d iterations, h up to %d", tag,
+                           res.iterations, res.h_max);
+                    int64_t a = 0, d = 0, sl = 0, sc = 0;
+                    lbfgs_spec_stats(c, &a, &d);
+                    lbfgs_search_stats(c, &sl, &sc);
+                    EXPECT(mode == 3 || a + d == 0, "%s: speculative launches outside the speculative mode", tag);
+                    // queued launches only while h <= 16: one per iteration at the most
+                    EXPECT(a <= 16, "%s: %lld queued launches taken with 16 cooperative iterations", tag, (long long)a);
+                    EXPECT(mode == 3 || mode == 4 || sl == 0, "%s: device searches outside the small-n forms", tag);
+                    adopted += a;
+                    searches += sl;
+                    lbfgs_ctx_destroy(c);
+                }
+            }
+    EXPECT(adopted > 0 && searches > 0, "long history: %lld queued launches taken, %lld device searches",
+           (long long)adopted, (long long)searches);
+    std::printf("long history: %lld queued launches taken, %lld device searches, %.0f s\n", (long long)adopted,
+                (long long)searches, (double)(std::clock() - t0) / CLOCKS_PER_SEC);
+    setenv("LBFGS_DOUBLE_SMALL", "0", 1);
+    setenv("LBFGS_SPEC", "1", 1);
+    setenv("LBFGS_DOUBLE_TWOLOOP", "0", 1);
+    lbfgs_constants k;
+    lbfgs_constants_cuda(&k);
+    for (int cuda = 1; cuda <= 2; ++cuda) {  // cu_alpha / cu_rho [MMAX], the slot k % m wrapping at k = 64
+        const int64_t n = 1537;
+        const int m = 64, ls = cuda == 1 ? LBFGS_LS_WOLFE : LBFGS_LS_BACKTRACKING;
+        const auto x0 = x0_for(n, 1);
+        lbfgs_ctx* c = nullptr;
+        EXPECT(lbfgs_ctx_create(&c, n, m, 0) == 0, "create");
+        if (!c) continue;
+        std::vector<double> x(n);
+        lbfgs_result res;
+        const unsigned flags = LBFGS_FLAG_QUIET | LBFGS_FLAG_TRACE | LBFGS_FLAG_CUDA_COMPAT |
+                               (cuda == 2 ? LBFGS_FLAG_CUDA_VARIANT : 0u);
+        const int st = lbfgs_minimize(c, LBFGS_OBJ_ROSENBROCK, nullptr, ls, &k, x0.data(), x.data(), maxit, tol, flags,
+                                      &res);
+        char tag[64];
+        std::snprintf(tag, sizeof tag, "long history cuda=%d", cuda);
+        EXPECT(st >= 0, "%s: %d %s", tag, st, lbfgs_last_error(c));
+        if (st >= 0)
+            compare(tag, c, st, x, res, oracle(ORC_OBJ_ROSENBROCK, ls, n, m, maxit, x0, nullptr, nullptr, nullptr, cuda, tol));
+        EXPECT(res.iterations > m, "%s: %d iterations do not wrap the ring", tag, res.iterations);
+        lbfgs_ctx_destroy(c);
+    }
 }
 
 // host callbacks: the reference call sequence call for call, and one call per point by default
@@ -418,6 +498,7 @@ static void cxx_dropin() {
 int main() {
     device_objectives();
     cuda_paths();
+    long_history();
     host_callbacks();
     dense_objective();
     api_surface();

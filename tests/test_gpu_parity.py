@@ -21,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cuda-lbfgs_amd"))
 import lbfgs_amd as L  # noqa: E402
 import oracle_lib as O  # noqa: E402
+import hist_cases as HC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -95,17 +96,28 @@ def test_trial_bit_exact(obj, n):
     assert bits([dphi])[0] == bits([O.dot(gref, d, O.CANON)])[0]
 
 
-@pytest.mark.parametrize("h", [1, 2, 5])
+@pytest.mark.parametrize("h", [1, 2, 5, 17, 64])
 @pytest.mark.parametrize("n", [3, 1000, 70_001])
 def test_twoloop_bit_exact(h, n):
-    rs = np.random.RandomState(100 * h + n)
-    g = rs.uniform(-1, 1, n)
-    S = [rs.uniform(-1, 1, n) for _ in range(h)]
-    Y = [s * rs.uniform(0.5, 2.0, n) + 0.01 * rs.uniform(-1, 1, n) for s in S]  # s.y > 0
-    d, gd = ctx(n, 5).twoloop(g, S, Y)
+    """h = 17: the first history past the cooperative forms' 16 pairs; h = 64: the driver's limit, result
+    slots up to SLOT_B0(64) + 63"""
+    g, S, Y = HC.twoloop_inputs(h, n)
+    d, gd = ctx(n, 5 if h <= 5 else 64).twoloop(g, S, Y)
     dref, gdref = O.twoloop(g, S, Y, O.CANON)
     assert np.array_equal(bits(d), bits(dref))
     assert bits([gd])[0] == bits([gdref])[0]
+
+
+@pytest.mark.parametrize("h,n", HC.TWOLOOP_LONG)
+def test_twoloop_long_history_against_long_double(h, n):
+    """The device two-loop against the same recursion in numpy.longdouble, left to right. The bound is 18
+    times the oracle's own largest difference on these inputs and is asserted for the oracle alone, on
+    the CPU, in tests/test_history_inputs.py; it is not taken from the GPU."""
+    g, S, Y = HC.twoloop_inputs(h, n)
+    d, _ = ctx(n, 64).twoloop(g, S, Y)
+    err = HC.twoloop_error(d, HC.twoloop_longdouble(g, S, Y))
+    print(f"two-loop h={h} n={n}: relative difference to long double {err:.3g}")
+    assert np.all(np.isfinite(d)) and err <= HC.TWOLOOP_BOUND, (h, n, err)
 
 
 @pytest.mark.parametrize("k", [10, 30, 60])
